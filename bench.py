@@ -5,10 +5,13 @@ autoregressive Text2Mel decode (exact-parity incremental algorithm), one SSRN pa
 linear spectrogram; inputs (character ids) and weights are resident in HBM before the timed region.
 Multi-GPU: utterances shard embarrassingly, 32 per GPU, no collective on the data path ("weak").
 
-    python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2                      # set up, warm up, time the steps, print the line
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR   # + the last timed step's Y, max_attentions, Z (a seeded sample of its rows) as DIR/*.npy
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full               # + everything below that takes passes of its own
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 
-What the JSON line holds besides the contract's fields (everything is measured in this run unless it says otherwise):
+A plain run's line holds the contract's fields, `config`, `roofline` as far as the timed region itself yields it, and per rank whether its decodes ran on the
+team kernels.  What --full adds (everything is measured in this run unless it says otherwise):
   roofline            the kernel that dominates the step by TIME (rocprofv3 --stats: profiles/r06_kernel_stats.md): xcone_kernel, the re-evaluation of
                       AudioDec's dependency cone on the decode's side stream; HIP-event timed on ITS stream inside the timed region (every 16th
                       frame from frame 100 on), fp32-MFMA bound; `frac` = the whole launch, `frac_gemm_phase` = its GEMM layers' own phases (in-kernel stamps);
@@ -245,6 +248,26 @@ def timed(fn, reps=3):
     return e0.elapsed_time(e1) / reps
 
 
+DUMP_Z_BYTES = 48 * 1000 * 1000    # --dump-outputs: Z's share of the 64 MB (Y and the trajectory of a B=32, T=210 step take 2.2 MB)
+
+
+def dump_outputs(path, Y, Z, mx):
+    """--dump-outputs: what synthesize() returned in the last timed step, as float32 .npy files: Y (B, T, 80), max_attentions (B, T; integers, exact in
+    float32) and Z (B, 4T, 1025) as its B * 4T rows.  Of a Z above DUMP_Z_BYTES (the default step's is 110 MB) a fixed, seeded sample of the rows is
+    written, in ascending row order; Z_rows (float64) holds the written rows' indices into Z.reshape(-1, 1025)."""
+    os.makedirs(path, exist_ok=True)
+    rows = Z.reshape(-1, Z.shape[-1])
+    keep = DUMP_Z_BYTES // (4 * rows.shape[1])
+    if rows.shape[0] > keep:
+        idx = np.sort(np.random.default_rng(1234).choice(rows.shape[0], size=keep, replace=False))
+        rows = rows[torch.from_numpy(idx).to(rows.device)]
+    else:
+        idx = np.arange(rows.shape[0])
+    for name, a in (("Y", Y), ("max_attentions", mx), ("Z", rows)):
+        np.save(os.path.join(path, name + ".npy"), a.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "Z_rows.npy"), idx.astype(np.float64))
+
+
 def cached_synthetic_weights(hp, seed, rank, world):
     """The seeded random-init weights (209.5 MB, ~3 s to draw): rank 0 draws them once per box and leaves them in /tmp, the other ranks (and the
     runs at the next N) load the file instead of drawing the same numbers again."""
@@ -288,6 +311,9 @@ def main():
     ap.add_argument("--no-extras", action="store_true", help="skip the untimed per-kernel passes and the other BASELINE configs")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL; the driver's multi-GPU runs) or gloo (plumbing test: ranks may share a GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="testing only: every rank uses cuda:0")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run everything else this file measures (the host gather, placement census, in-kernel "
+                                                        "stamps, phases, per-kernel passes, other configs, CPU baseline, vocoder); the --no-* options trim that")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (rank 0's shard) as DIR/<name>.npy, float32, at most 64 MB in all")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -394,32 +420,37 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)                     # measurement only: no collective on the data path
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, Y, Z, mx)
 
     # ---- the host gather of SURVEY 8e, timed separately (never part of `value`): every rank's Z -> its pinned host buffer ->
     #      rank 0's host (gloo); with one rank this is the plain D2H copy
-    Zh = torch.empty(Z.shape, dtype=Z.dtype, pin_memory=True)
-    barrier()
-    tg0 = time.perf_counter()
-    gathered = gather_to_host(Z, Zh, host_group, world, rank)
-    if world > 1:
-        dist.barrier()
-    gather_s = time.perf_counter() - tg0
-    if world > 1:
-        t = torch.tensor([gather_s], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        gather_s = float(t.item())
-    if rank == 0 and world > 1:
-        assert gathered is not None and tuple(gathered.shape) == (world * B, Z.shape[1], Z.shape[2])
+    if args.full:
+        Zh = torch.empty(Z.shape, dtype=Z.dtype, pin_memory=True)
+        barrier()
+        tg0 = time.perf_counter()
+        gathered = gather_to_host(Z, Zh, host_group, world, rank)
+        if world > 1:
+            dist.barrier()
+        gather_s = time.perf_counter() - tg0
+        if world > 1:
+            t = torch.tensor([gather_s], dtype=torch.float64, device="cuda" if args.dist_backend == "nccl" else "cpu")
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            gather_s = float(t.item())
+        if rank == 0 and world > 1:
+            assert gathered is not None and tuple(gathered.shape) == (world * B, Z.shape[1], Z.shape[2])
 
-    # ---- placement: where a 128-block launch lands (the team kernels' speed rests on blocks b, b + 8, ... sharing an XCD and on 256 co-resident workgroups;
-    #      their correctness does not), and whether THIS rank's timed decodes ran on the team kernels -- from every rank, not only rank 0
-    xcc, n_cu = eng.debug_xcd_census()
-    k0 = int(xcc[0])
-    nx = int(xcc.max()) + 1
-    mine = {"rank": rank, "decode_team_kernels": fallback is None, "status_report": fallback, "compute_units": n_cu, "xcds_seen": int(len(set(xcc.tolist()))),
-            "blocks_b_and_b_plus_8_share_an_xcd": bool(all(int(xcc[b]) == int(xcc[b % 8]) for b in range(128))),
-            "round_robin_from_block_0": bool(nx > 1 and all(int(xcc[b]) == (k0 + b) % nx for b in range(128))),
-            "team_kernels_state_bits": eng.debug_team_kernels_state()}
+    # ---- placement: whether THIS rank's timed decodes ran on the team kernels -- from every rank, not only rank 0 -- and with --full where a 128-block launch
+    #      lands (the team kernels' speed rests on blocks b, b + 8, ... sharing an XCD and on 256 co-resident workgroups; their correctness does not)
+    mine = {"rank": rank, "decode_team_kernels": fallback is None, "status_report": fallback}
+    if args.full:
+        xcc, n_cu = eng.debug_xcd_census()
+        k0 = int(xcc[0])
+        nx = int(xcc.max()) + 1
+        mine.update({"compute_units": n_cu, "xcds_seen": int(len(set(xcc.tolist()))),
+                     "blocks_b_and_b_plus_8_share_an_xcd": bool(all(int(xcc[b]) == int(xcc[b % 8]) for b in range(128))),
+                     "round_robin_from_block_0": bool(nx > 1 and all(int(xcc[b]) == (k0 + b) % nx for b in range(128))),
+                     "team_kernels_state_bits": eng.debug_team_kernels_state()})
     if world > 1:
         ranks = [None] * world
         dist.all_gather_object(ranks, mine, group=host_group)
@@ -461,7 +492,7 @@ def main():
                         frac_hbm=round(alg_bytes / (avg * 1e-3) / 1e9 / PEAK_HBM_GBPS, 5))
         # (a) the launch also carries the two row phases (no MFMA work) and its barriers / row passes: the GEMM layers' own phases from in-kernel stamps of one
         #     steady-state launch (an untimed extra decode), so that `frac` (whole launch, event-timed) and `frac_gemm_phase` can be told apart
-        if chain_prof and not args.no_extras and roof.get("flop_per_launch"):
+        if args.full and chain_prof and not args.no_extras and roof.get("flop_per_launch"):
             st = xcone_phase_stamps(eng, L, T)
             if st:
                 tfg = roof["flop_per_launch"] / (st["gemm"] * 1e-6) / 1e12
@@ -493,17 +524,18 @@ def main():
             "pipeline_tflops": round(value * flop_frame / 1e12, 2),
             "pipeline_frac_of_f32_mfma_peak": round(value * flop_frame / 1e12 / (PEAK_F32_MFMA_TFLOPS * world), 4),
             "roofline": roof, "device_bytes": eng.device_bytes(), "placement": ranks,
-            "gather": {"what": "every rank's Z (B,4T,1025) -> its pinned host buffer (D2H) -> rank 0's host over gloo (SURVEY 8e); one rank: the D2H copy",
-                       "bytes_per_rank": Z.numel() * 4, "seconds": round(gather_s, 5),
-                       "value_incl_gather": round(world * B * T / (elapsed / args.steps + gather_s), 1),
-                       "note": "serial upper bound on the cost: the gather of batch n can overlap the compute of batch n+1"},
         }
-        if not args.no_extras:
-            out.update(extras(eng, args, hp, W, L, Y, Z, B, T, gm, ms_step))
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(hp, W)
-        if world == 1 and not args.no_vocoder:
-            out["vocoder"] = vocoder_section(hp, Z, ms_step, not args.no_cpu_baseline)
+        if args.full:
+            out["gather"] = {"what": "every rank's Z (B,4T,1025) -> its pinned host buffer (D2H) -> rank 0's host over gloo (SURVEY 8e); one rank: the D2H copy",
+                             "bytes_per_rank": Z.numel() * 4, "seconds": round(gather_s, 5),
+                             "value_incl_gather": round(world * B * T / (elapsed / args.steps + gather_s), 1),
+                             "note": "serial upper bound on the cost: the gather of batch n can overlap the compute of batch n+1"}
+            if not args.no_extras:
+                out.update(extras(eng, args, hp, W, L, Y, Z, B, T, gm, ms_step))
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(hp, W)
+            if world == 1 and not args.no_vocoder:
+                out["vocoder"] = vocoder_section(hp, Z, ms_step, not args.no_cpu_baseline)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

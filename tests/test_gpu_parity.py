@@ -756,7 +756,7 @@ def test_bench_two_ranks_through_torch_distributed_run():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29633",
            os.path.join(root, "bench.py"), "--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
-           "--batch", "8", "--max-T", "24", "--no-cpu-baseline", "--no-vocoder", "--no-extras"]
+           "--batch", "8", "--max-T", "24", "--full", "--no-cpu-baseline", "--no-vocoder", "--no-extras"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

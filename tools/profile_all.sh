@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 STEPS=${STEPS:-012345789}           # e.g. STEPS=127 bash tools/profile_all.sh: only the bench line, the kernel trace and the layer table
 want() { case "$STEPS" in *$1*) return 0;; *) return 1;; esac; }
 # 1. the bench line (metric, roofline of the time-dominant kernel, kernels, other configs, cpu_baseline, vocoder)  -> profiles/r06_bench.json
-want 1 && timeout 600 python "$R/bench.py" > "$OUT/bench.json" 2> "$OUT/bench.err"
+want 1 && timeout 600 python "$R/bench.py" --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 cd /tmp
 # 2. per-kernel time of the same workload                                               -> profiles/r06_kernel_stats.{csv,md}
 want 2 && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/kernel_stats" -- \
@@ -45,7 +45,7 @@ want 9 && for tail in 2 7 6 5; do
   DCTTS_CHAIN_TAIL=$tail DCTTS_PIECETIME=150 GM=0 HP=1 NREP=1 timeout 120 python tools/decode_time.py 2>&1 | grep -E "frame 15[0-7]" | tail -8
 done > "$OUT/chain_tail_split.txt" 2>&1
 # ... and the two parts of the one-launch chain piece timed as launches of their own (DCTTS_CHAIN_TAIL=6: xtail_kernel + xgroup_kernel, HIP events, bench.py's kernels[])
-want 9 && (echo "== DCTTS_CHAIN_TAIL=6: bench.py kernels[] (xtail_kernel, xgroup_kernel: avg_launch_ms)"; DCTTS_CHAIN_TAIL=6 timeout 400 python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-vocoder 2>/dev/null | \
+want 9 && (echo "== DCTTS_CHAIN_TAIL=6: bench.py kernels[] (xtail_kernel, xgroup_kernel: avg_launch_ms)"; DCTTS_CHAIN_TAIL=6 timeout 400 python bench.py --steps 3 --warmup 1 --full --no-cpu-baseline --no-vocoder 2>/dev/null | \
   python -c "import json,sys; j=json.loads(sys.stdin.readlines()[-1]); [print(k['kernel'][:60], '| launches', k['launches'], '| avg_launch_ms', k['avg_launch_ms']) for k in j.get('kernels', []) if 'decode chain' in k['kernel']]; print('decode_us_per_step', j['phases']['decode_us_per_step'])") >> "$OUT/chain_tail_split.txt" 2>&1
 # 10. the MFMA feed lab (what a wave keeps of the matrix pipe when its operands arrive during the loop) and the first-decode / stream-pair probes
 want 0 && (hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/micro/mfma_feed_lab.hip -o tools/micro/kp_mfma_feed_lab 2> "$OUT/mfma_feed_lab_build.log"; timeout 120 tools/micro/kp_mfma_feed_lab > "$OUT/mfma_feed_lab.txt" 2>&1)
