@@ -53,6 +53,7 @@ SYMBOLS = {
     "dctts_set_decode_mode": (c_int, [c_void_p, c_int]),
     "dctts_device_bytes": (c_size_t, [c_void_p]),
     "dctts_debug_layer": (c_int, [c_void_p, ctypes.c_char_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "dctts_debug_conv_forms": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_longlong)]),
     "dctts_debug_seed_prev_max": (c_int, [c_void_p, c_void_p, c_int]),
     "dctts_debug_copy": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),
     "dctts_debug_set_trace": (c_int, [c_void_p, c_int, ctypes.c_char_p]),

@@ -24,7 +24,6 @@
 #include "decode_fallback_kernels.h"
 #include "decode3_kernels.h"
 #include "hconv_kernel.h"
-#include "hconv16_kernel.h"
 #include "xgroup_kernel.h"
 #include "xcone_kernel.h"
 #include "xmlp_kernel.h"
@@ -144,23 +143,6 @@ hipError_t launch_hconv_cols(const ConvShape& s, const ConvParams& p, hipStream_
   return hipGetLastError();
 }
 
-#define HCONV16_CASE(E, NT_, NW_, BD_, SB_)                                                                   \
-  if (s.epi == E && s.nt == NT_ && s.nw == NW_) {                                                             \
-    hipLaunchKernelGGL((hconv16_kernel<E, NT_, NW_, BD_, SB_>), grid, dim3(NW_ * 64), 0, stream, p, m_start); \
-    return hipGetLastError();                                                                                 \
-  }
-
-hipError_t launch_hconv16(const ConvShape& s, const ConvParams& p, int m_start, hipStream_t stream) {
-  if (p.M <= m_start) return hipSuccess;
-  const dim3 grid((p.M - m_start + 15) / 16);
-  HCONV16_CASE(EPI_HC, 4, 8, 2, 0)
-  HCONV16_CASE(EPI_HC, 8, 8, 2, 0)
-  HCONV16_CASE(EPI_HC, 16, 8, 1, 1)
-  HCONV16_CASE(EPI_C, 8, 8, 2, 0)
-  HCONV16_CASE(EPI_C, 6, 11, 2, 1)
-  return hipErrorInvalidConfiguration;
-}
-
 }  // namespace dctts
 
 // ------------------------------------------------------------------------------------------------
@@ -194,7 +176,7 @@ struct DevLayer {
   int ntaps = 1, cin = 0, cin_p = 0, tap_off[3] = {0, 0, 0}, cout = 0, act = ACT_NONE;
   float *wp = nullptr, *bias = nullptr, *g1 = nullptr, *b1 = nullptr, *g2 = nullptr, *b2 = nullptr;
   bool deconv_phase = false; int phase = 0;
-  float* wp16r = nullptr;         // SSRN 4T-resolution layers: packing for hconv16_kernel (row-tail launches)
+  bool row_tail = false;          // SSRN 4T-resolution layers: the k = 1 layers among them may run their left-over rows as thirds of K (run_conv)
   float* wpb = nullptr;           // opt-in split-bf16 form (dctts_set_split_bf16): the kernel as bf16 (hi, mid) fragments for v_mfma_f32_32x32x16_bf16; the 1025-column layers: their first 1024 columns
   float* wpx = nullptr; float* wxcol = nullptr;   // SSRN's 1025-column layers: the first 1024 columns as 32 tiles + the last column's weights (hconv_kernel<..., XC = 1>); the row tail keeps wp
   bool col_split = false;         // TextEnc's three-tap highway layers: when the 32-row items fill less than 3/4 of the CUs the layer runs as quarter-COLUMN items + a finishing pass (run_conv)
@@ -317,6 +299,7 @@ struct dctts_ctx {
   unsigned* wait_ctr = nullptr;        // device memory, polled in-kernel: [0] chain pieces done + 1, [32] bulk pieces complete (written by xcone_kernel's last team, or a write-value operation), [64] error word
   hipGraph_t graph = nullptr; hipGraphExec_t graph_exec = nullptr; std::string graph_geom;   // decode mode 0: one step, replayed T times
   long long prof_rows = 0;             // output rows covered by the profiled launches since prof_enable
+  long long conv_forms[7] = {0, 0, 0, 0, 0, 0, 0};   // output rows run_conv gave to each launch form since the last dctts_debug_conv_forms (indices: DCTTS_FORM_*)
   int n_cu = 256;                      // CUs of the device (hipDeviceProp_t::multiProcessorCount)
   int bf16_packed = 0;                 // dctts_set_split_bf16 before finalize: 1 = SSRN's layers carry the bf16 packing, 2 = TextEnc's as well
   int bf16_mode = 0;                   // ... and what runs: 0 = exact fp32 (default), 1 = SSRN on the split-bf16 form, 2 = SSRN + TextEnc
@@ -491,7 +474,7 @@ static int make_C(dctts_ctx* c, const std::string& scope, int cin_real, int cin_
   if (dec) CHK(upload(c, k->v, &L->wraw));
   if (tail) {
     L->shape16 = pick_shape16(EPI_C, cout);
-    CHK(upload(c, pack_bw(W, 1, cin_real, L->cin_p, L->shape16.nt * L->shape16.nw, cout, false, 16), &L->wp16r));
+    L->row_tail = true;
   }
   if (c->pack_bf16_now) {
     if (cout == 1025) CHK(upload(c, pack_bw_bf16(W, 1, cin_real, L->cin_p, 32, 1024, false), &L->wpb));      // + wxcol below: the last column stays an fp32 dot product
@@ -533,7 +516,7 @@ static int make_HC(dctts_ctx* c, const std::string& scope, int C, int k, int rat
   }
   if (tail) {
     L->shape16 = pick_shape16(EPI_HC, C);
-    CHK(upload(c, pack_bw(W, k, C, L->cin_p, L->shape16.nt * L->shape16.nw, C, true, 16), &L->wp16r));
+    L->row_tail = true;
   }
   if (c->pack_bf16_now) CHK(upload(c, pack_bw_bf16(W, k, C, L->cin_p, L->shape.nt * L->shape.nw, C, true), &L->wpb));
   L->hc = true;
@@ -594,7 +577,8 @@ static void read_env(dctts_ctx* c) {
   auto geti = [](const char* n, int* v) { if (const char* e = getenv(n)) *v = atoi(e); };
   geti("DCTTS_SYNC_VALUES", &c->sync_values); geti("DCTTS_CHAIN_WAIT", &c->chain_wait_inkernel); geti("DCTTS_XGROUP", &c->xgroup); geti("DCTTS_XCONE", &c->xcone); geti("DCTTS_CHAIN_TAIL", &c->chain_tail);
   geti("DCTTS_TRACE", &c->trace_frame);
-  if (c->chain_tail == 7) { c->chain_tail = 2; c->tail_np = 3; }      // 7 = the default form with round 5's split of the cone (A/B) geti("DCTTS_PIECETIME", &c->piecetime);
+  geti("DCTTS_PIECETIME", &c->piecetime);
+  if (c->chain_tail == 7) { c->chain_tail = 2; c->tail_np = 3; }      // 7 = the default form with round 5's split of the cone (A/B)
   if (const char* e = getenv("DCTTS_TRACE_FILE")) c->trace_file = e;
   // rocprofv3 --pmc serialises dispatches ACROSS queues: a launch that polls the other stream's counter would never see it move
   // (it only times out, with wrong results).  Under counter collection the two decode streams meet through events instead.
@@ -811,7 +795,7 @@ extern "C" int dctts_weights_finalize(dctts_ctx* c) {
       snprintf(nm, 64, "D_%d", i++); L = DevLayer(); L2 = DevLayer(); CHK(make_D(c, s + nm, cc, &L, &L2)); c->ssrn.push_back(L); c->ssrn.push_back(L2);
       for (int j = 0, r = 1; j < 2; ++j, r *= 3) { snprintf(nm, 64, "HC_%d", i++); L = DevLayer(); CHK(make_HC(c, s + nm, cc, 3, r, false, &L, false, rep == 1)); L.tap_tail = true; c->ssrn.push_back(L); }
     }
-    // everything from HC_8 on runs at 4T rows: those layers also get the 16-row packing for the row-tail launch
+    // everything from HC_8 on runs at 4T rows: those layers are marked for the row-tail launch (DevLayer::row_tail, shape16 = the tail's profiling id)
     snprintf(nm, 64, "C_%d", i++); L = DevLayer(); CHK(make_C(c, s + nm, cc, cc, 2 * cc, ACT_NONE, &L, false, true)); c->ssrn.push_back(L);
     for (int rep = 0; rep < 2; ++rep) { snprintf(nm, 64, "HC_%d", i++); L = DevLayer(); CHK(make_HC(c, s + nm, 2 * cc, 3, 1, false, &L, false, true)); L.tap_tail = true; c->ssrn.push_back(L); }
     snprintf(nm, 64, "C_%d", i++); L = DevLayer(); CHK(make_C(c, s + nm, 2 * cc, 2 * cc, F, ACT_NONE, &L, false, true)); c->ssrn.push_back(L);
@@ -903,7 +887,10 @@ static int run_conv(dctts_ctx* c, const DevLayer& L, const View& in, const int* 
   // Row split: exact rounds of 32-row items on hconv_kernel; what is left over
   //   * of a highway layer with three taps, when three times as many workgroups still fit in two rounds: 32-row items x TAPS + a finishing pass
   //     (hconv_kernel.h: RAW) -- a third of an item's time per round instead of a whole one;
-  //   * of the 4T-resolution k = 1 layers, when it is at most 0.6 of a round: 16-row items (hconv16_kernel.h).
+  //   * of the 4T-resolution k = 1 layers, under the same condition: 32-row items x THIRDS OF K + a finishing pass.
+  // Anything else (a left-over of more than 2/3 of a round, layers without a tail form) runs all its items on hconv_kernel, the last round partial.
+  // (Rounds 1-3 had a third form, 16-row items for a left-over of at most 0.6 of a round; every layer that carried it has a tap / K-third tail, whose
+  //  condition 3 left <= 2 n covers left <= 0.6 n, so no launch reached it any more: removed, tests/test_gpu_launch_forms.py holds the census.)
   int tiles32 = (p.M + 31) / 32, m_tail = p.M;
   // The opt-in split-bf16 form (dctts_set_split_bf16): whole 32-row items for every row, contraction on the bf16 matrix pipe.  `bf` is set by the network drivers
   // for TextEnc / SSRN only; the layer must carry the packing.
@@ -918,6 +905,7 @@ static int run_conv(dctts_ctx* c, const DevLayer& L, const View& in, const int* 
       p.m_base = 0; p.raw_out = *buf; p.raw_ld = 2 * L.cout;
     }
     HIPCHK(launch_hconv_bf16(L.shape, p, st));
+    c->conv_forms[DCTTS_FORM_SPLIT_BF16] += p.M;
     if (prof) { HIPCHK(hipEventRecord(e1, st)); c->prof_ev.emplace_back(e0, e1); c->prof_cnt.push_back(1); c->prof_rows += p.M; }
     return 0;
   }
@@ -931,23 +919,24 @@ static int run_conv(dctts_ctx* c, const DevLayer& L, const View& in, const int* 
     if (need > c->cols_ws_floats) CHK(grow_scratch(c, &c->cols_ws, &c->cols_ws_floats, need));
     p.m_base = 0; p.raw_out = c->cols_ws; p.raw_ld = raw_ld;
     HIPCHK(launch_hconv_cols(L.shape, p, st));
+    c->conv_forms[DCTTS_FORM_COL_SPLIT] += p.M;
     if (prof) { HIPCHK(hipEventRecord(e1, st)); c->prof_ev.emplace_back(e0, e1); c->prof_cnt.push_back(1); c->prof_rows += p.M; }
     return 0;
   }
   const int full = (tiles32 / c->n_cu) * c->n_cu, left = tiles32 - full;
   const bool hc3 = L.tap_tail && L.shape.epi == EPI_HC && L.ntaps == 3 && !gather && (L.shape.nt == 2 || L.shape.nt == 4 || L.shape.nt == 8) && (L.cout % 256) == 0 && L.cout <= 1024;
-  // ... and of the 4T-resolution k = 1 layers of SSRN (the ones that carry the 16-row packing): thirds of K instead of taps, same finishing idea
-  const bool c3 = L.wp16r && L.shape.epi == EPI_C && L.ntaps == 1 && !gather && !L.deconv_phase && L.cout <= 1280 &&
+  // ... and of the 4T-resolution k = 1 layers of SSRN: thirds of K instead of taps, same finishing idea
+  const bool c3 = L.row_tail && L.shape.epi == EPI_C && L.ntaps == 1 && !gather && !L.deconv_phase && L.cout <= 1280 &&
                   ((L.shape.nt == 4 && L.shape.nw == 8) || (L.shape.nt == 3 && L.shape.nw == 11));
   const bool tap_tail = (hc3 || c3) && left > 0 && 3 * left <= 2 * c->n_cu && !rm.step;      // (not in decode mode 0's captured launches: the partial-sum buffer is allocated on demand)
   if (tap_tail) { tiles32 = full; m_tail = full * 32; }
-  else if (L.wp16r && left * 10 <= c->n_cu * 6) { tiles32 = full; m_tail = full * 32; }
   if (L.wpx) { p.wp = L.wpx; p.wx = L.wxcol; }      // (the main launch only: the row tail below keeps the 33-tile packing)
   HIPCHK(launch_hconv(L.shape, p, st, tiles32));
+  c->conv_forms[L.wpx ? DCTTS_FORM_XC : DCTTS_FORM_MAIN] += m_tail < p.M ? m_tail : p.M;
   p.wp = L.wp; p.wx = nullptr;
   if (prof) { HIPCHK(hipEventRecord(e1, st)); c->prof_ev.emplace_back(e0, e1); c->prof_cnt.push_back(1); c->prof_rows += m_tail < p.M ? m_tail : p.M; }
   if (m_tail < p.M && tap_tail) {
-    // the row tail of a big highway layer: 32-row items x taps + a finishing pass (hconv_kernel.h: RAW) instead of 16-row items
+    // the row tail of a big highway layer: 32-row items x taps + a finishing pass (hconv_kernel.h: RAW)
     const int raw_ld = (L.shape.epi == EPI_HC) ? 2 * L.cout : round_up(L.cout, 32);
     const size_t need = (size_t)3 * (p.M - m_tail) * raw_ld;
     if (need > c->tail_ws_floats) CHK(grow_scratch(c, &c->tail_ws, &c->tail_ws_floats, need));
@@ -956,13 +945,7 @@ static int run_conv(dctts_ctx* c, const DevLayer& L, const View& in, const int* 
     hipEvent_t t0 = nullptr, t1 = nullptr;
     if (prof16) { HIPCHK(hipEventCreate(&t0)); HIPCHK(hipEventCreate(&t1)); HIPCHK(hipEventRecord(t0, st)); }
     HIPCHK(launch_hconv_tail(L.shape, p, st));
-    if (prof16) { HIPCHK(hipEventRecord(t1, st)); c->prof_ev.emplace_back(t0, t1); c->prof_cnt.push_back(1); c->prof_rows += p.M - m_tail; }
-  } else if (m_tail < p.M) {
-    p.wp = L.wp16r;
-    const bool prof16 = (c->prof_id == 50000 + L.shape16.epi * 10000 + L.shape16.nt * 100 + L.shape16.nw);      // the 16-row tail launch of the same layer
-    hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (prof16) { HIPCHK(hipEventCreate(&t0)); HIPCHK(hipEventCreate(&t1)); HIPCHK(hipEventRecord(t0, st)); }
-    HIPCHK(launch_hconv16(L.shape16, p, m_tail, st));
+    c->conv_forms[L.shape.epi == EPI_HC ? DCTTS_FORM_HC_TAP_TAIL : DCTTS_FORM_C_TAP_TAIL] += p.M - m_tail;
     if (prof16) { HIPCHK(hipEventRecord(t1, st)); c->prof_ev.emplace_back(t0, t1); c->prof_cnt.push_back(1); c->prof_rows += p.M - m_tail; }
   }
   return 0;
@@ -1295,6 +1278,13 @@ extern "C" int dctts_debug_layer(dctts_ctx* c, const char* net, int index, const
   return run_conv(c, L, vi, nullptr, vo, rm, st);
 }
 
+// Census of run_conv's launch forms (tests/test_gpu_launch_forms.py): output rows per form since the previous call; reading clears the counters.
+extern "C" int dctts_debug_conv_forms(dctts_ctx* c, long long rows[7]) {
+  if (!c || !rows) return fail(DCTTS_ERR_ARG, "conv_forms: null argument");
+  std::lock_guard<std::recursive_mutex> lk_(c->mu);
+  for (int i = 0; i < 7; ++i) { rows[i] = c->conv_forms[i]; c->conv_forms[i] = 0; }
+  return 0;
+}
 
 // Calibration aid for the HBM counters (FETCH_SIZE / WRITE_SIZE): a float4 grid-stride copy of known size.
 __global__ void __launch_bounds__(256) calib_copy_kernel(const float4* __restrict__ src, float4* __restrict__ dst, size_t n4) {

@@ -1286,9 +1286,10 @@ static int decode_v3(dctts_ctx* c, const DecodeWs& w, int B, int N, int T, hipSt
   // the chain's last piece is on `st`; the bulk stream's last piece was consumed by it, so `st` is ordered after all decode work.
   c->fin_xerr = (c->xg_on || c->xc_on) ? xg_mem(c, B).err : nullptr;      // this decode's error words, folded into the sticky status by decode_finish
   c->fin_werr = cwait ? (const int*)(c->wait_ctr + 64) : nullptr;
-  if (pt0 >= 0 && pt0 + 8 < T) {
-    HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipStreamSynchronize(sb));
-    for (int i = 0; i < 8; ++i) {
+  if (pt0 >= 0) {
+    const int npt = T - pt0 < 8 ? T - pt0 : 8;      // frames of the window this decode ran (a decode shorter than the window reports the ones it has)
+    if (npt > 0) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipStreamSynchronize(sb)); }
+    for (int i = 0; i < npt; ++i) {
       float dc = 0, db = 0, c2c = 0, b2c = 0, c2b = 0;
       (void)hipEventElapsedTime(&dc, pe_c[i][0], pe_c[i][1]);
       if (i > 0) { (void)hipEventElapsedTime(&db, pe_b[i][0], pe_b[i][1]); (void)hipEventElapsedTime(&c2c, pe_c[i - 1][1], pe_c[i][0]);

@@ -125,7 +125,7 @@ class Engine:
         return n.value, ms.value
 
     def prof_rows(self) -> int:
-        """Output rows covered by the profiled launches since prof_enable (a layer may be split with a 16-row tail launch)."""
+        """Output rows covered by the profiled launches since prof_enable (a layer's rows may be split between the main launch and a tap / K-third tail launch)."""
         r = ctypes.c_longlong(0)
         self._ok(self.lib.dctts_prof_rows(self._h, ctypes.byref(r)))
         return r.value
@@ -206,6 +206,14 @@ class Engine:
         out = self._new(B, upsample * T, cout)
         self._ok(self.lib.dctts_debug_layer(self._h, net.encode(), index, _ptr(X.contiguous()), B, T, _ptr(out), self._stream()))
         return out
+
+    CONV_FORMS = ("main", "xc", "col_split", "hc_tap_tail", "c_tap_tail", "rows16", "split_bf16")
+
+    def conv_forms(self) -> Dict[str, int]:
+        """Test hook (dctts_hip_debug.h): output rows each launch form of the layer launcher handled since the previous call (reading clears the counters)."""
+        rows = (ctypes.c_longlong * 7)()
+        self._ok(self.lib.dctts_debug_conv_forms(self._h, rows))
+        return dict(zip(self.CONV_FORMS, (int(r) for r in rows)))
 
     # ------------------------------------------------------------------ synthesize.py:45-57
     def _decode(self, call, check: bool):

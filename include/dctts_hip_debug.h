@@ -17,6 +17,20 @@ extern "C" {
  * each D layer occupying two consecutive indices.  Synchronises (allocates a scratch copy of X). */
 int dctts_debug_layer(dctts_ctx* ctx, const char* net, int index, const float* X, int B, int T, float* out, void* stream);
 
+/* Test hook: a census of the launch forms the layer launcher (run_conv in csrc/dctts_api.hip: every TextEnc / AudioEnc / AudioDec / SSRN layer outside the
+ * decode's team kernels) chose: rows[f] = the OUTPUT ROWS form f handled since the previous call of this function.  Reading clears the counters.  Host
+ * bookkeeping only (no device work, no synchronisation).  The forms:
+ *   MAIN         whole 32-row items on hconv_kernel (the last item may be ragged);
+ *   XC           the same for the 1025-column layers: 32 column tiles on the matrix pipe + the last column on the vector ALU;
+ *   COL_SPLIT    quarter-column items + hc_tail_finish_kernel (TextEnc's 512-channel highway layers, always);
+ *   HC_TAP_TAIL  the rows left over after exact rounds of an SSRN highway layer: 32-row items x 3 taps + hc_tail_finish_kernel;
+ *   C_TAP_TAIL   ... of SSRN's 4T-resolution k = 1 layers: 32-row items x thirds of K + c_tail_finish_kernel;
+ *   ROWS16       16-row items: the form was removed once this census showed that no launch reaches it; the slot stays, always 0;
+ *   SPLIT_BF16   the opt-in split-bf16 forms (dctts_set_split_bf16). */
+enum { DCTTS_FORM_MAIN = 0, DCTTS_FORM_XC = 1, DCTTS_FORM_COL_SPLIT = 2, DCTTS_FORM_HC_TAP_TAIL = 3, DCTTS_FORM_C_TAP_TAIL = 4, DCTTS_FORM_ROWS16 = 5,
+       DCTTS_FORM_SPLIT_BF16 = 6 };
+int dctts_debug_conv_forms(dctts_ctx* ctx, long long rows[7]);
+
 /* Test hook: the NEXT decode on this context (dctts_text2mel_decode / dctts_synthesize) starts from these prev_max_attentions
  * (host array, B values in [0, max_N)) instead of the reference's zeros (synthesize.py:46), then the seed is dropped.  Random weights
  * never walk the attention to the end of a 180-character text, so this is how tests put the window on keys max_N-3 .. max_N-1 at the
@@ -48,7 +62,8 @@ int dctts_debug_copy(const float* src, float* dst, size_t nfloats, void* stream)
  * kernel while enabled; collect() synchronises those events, returns the number of launches and their summed duration,
  * and clears the list.  kernel_id:
  *   epi*10000 + NT*100 + NW   every launch of hconv_kernel<epi, NT, NW> (epi 0 = C, 1 = HC), e.g. 10808 = SSRN HC_11 / HC_12;
- *   50000 + epi*10000 + NT*100 + NW   the 16-row tail launches hconv16_kernel<epi, NT, NW> of the layers that are split by rows, e.g. 61608 = HC_11 / HC_12's tail;
+ *   50000 + epi*10000 + NT*100 + NW   the row-tail launches (32-row items x taps or thirds of K + the finishing pass) of the layers that are split by rows; (epi, NT, NW)
+ *                             is the layer's 16-column-tile shape, the id its tail has had since it ran on 16-row items: e.g. 61608 = HC_11 / HC_12's tail;
  *   DCTTS_PROF_XGROUP         xgroup_kernel (a run of newest-row highway layers of the decode chain as one launch), on every 16th frame only;
  *                             prof_rows then counts LAYERS (10 for the AudioEnc run, the only run timed; the AudioDec layers are part of xtail_kernel's launch since round 4);
  *   DCTTS_PROF_XCONE          xcone_kernel (the tail of AudioDec's cone on the side stream), frames >= 100, every 16th; eager decode only (graph mode 0);
@@ -65,7 +80,7 @@ int dctts_debug_copy(const float* src, float* dst, size_t nfloats, void* stream)
 int dctts_prof_enable(dctts_ctx* ctx, int kernel_id);
 int dctts_prof_collect(dctts_ctx* ctx, int* launches, double* total_ms);
 /* Output rows those launches covered, summed since the last prof_enable (a layer's rows may be split between the
- * 32-row kernel -- the one timed here -- and a 16-row tail launch, see csrc/hconv16_kernel.h; decode kernels: rows = utterances
+ * main launch -- the one timed here -- and a tap / K-third tail launch, see run_conv in csrc/dctts_api.hip; decode kernels: rows = utterances
  * (chain) or cone rows (bulk) per launch). */
 int dctts_prof_rows(dctts_ctx* ctx, long long* rows);
 

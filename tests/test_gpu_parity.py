@@ -133,9 +133,10 @@ def test_layer_vs_oracle(weights, net, scope, causal, li):
     assert err < 2e-4, f"{net}/{l.scope}: max-abs {err}"
 
 
-# SSRN layers at 4T resolution are launched as exact rounds of 32-row items (hconv_kernel) + a tail of 16-row items
-# (hconv16_kernel).  The small cases above land entirely on the 16-row kernel; this case has one exact round for the
-# 32-row kernel plus a ragged tail (40 rows = 2 full 16-row items + one of 8 rows) for the other.
+# SSRN layers at 4T resolution are launched as exact rounds of 32-row items (hconv_kernel) + a tail of 32-row items x taps (highway layers) or
+# x thirds of K (k = 1 layers) with a finishing pass (hc_tail_finish_kernel / c_tail_finish_kernel).  The small cases above land entirely on that tail
+# form; this case has one exact round for the main kernel plus a ragged tail (40 rows = one full item + one of 8 rows) for the other.
+# (tests/test_gpu_launch_forms.py pins every form by name, with the launcher's own census.)
 SPLIT_CASES = []
 _seen = set()
 _ssrn = ssrn_layers(hp)
@@ -167,8 +168,8 @@ def test_layer_row_split(weights, li):
     assert got.shape == ref.shape
     # worst rows of either part, reported separately so a failure names the kernel
     flat_g, flat_r = got.reshape(B * T, -1), ref.reshape(B * T, -1)
-    e32 = maxabs(flat_g[: n_cu * 32], flat_r[: n_cu * 32]); e16 = maxabs(flat_g[n_cu * 32:], flat_r[n_cu * 32:])
-    assert e32 < 2e-4 and e16 < 2e-4, f"ssrn/{l.scope}: max-abs 32-row part {e32}, 16-row tail {e16}"
+    e32 = maxabs(flat_g[: n_cu * 32], flat_r[: n_cu * 32]); etail = maxabs(flat_g[n_cu * 32:], flat_r[n_cu * 32:])
+    assert e32 < 2e-4 and etail < 2e-4, f"ssrn/{l.scope}: max-abs main launch (exact round) {e32}, {'tap' if l.kind == 'HC' else 'K-third'} tail {etail}"
 
 
 # ---------------------------------------------------------------- network functions (the drop-in boundary)
@@ -282,7 +283,7 @@ def test_ssrn(weights):
 
 def test_ssrn_only_batch128_config3(weights):
     """BASELINE configs[2]: SSRN-only, batch 128, (128, 210, 80) -> (128, 840, 1025).  Determinism, agreement with the same
-    utterances run as shards of 32 (rows land on the 32-row or the 16-row MFMA kernel depending on the launch: fp32
+    utterances run as shards of 32 (rows land on the main launch or on the tap / K-third tail depending on the batch: fp32
     reassociation, <= 1e-5), range, and the oracle on two utterances."""
     eng = engine_for(weights)
     rng = np.random.default_rng(128)
@@ -562,8 +563,8 @@ def test_full_size_properties(weights):
     Ya, Za, mxa = eng.synthesize(L[:16].contiguous())
     Yb, Zb, mxb = eng.synthesize(L[16:].contiguous())
     assert torch.equal(torch.cat((Ya, Yb)), Y) and torch.equal(torch.cat((mxa, mxb)), mx)   # shards == whole batch, bitwise
-    # SSRN rows are served by the 32-row or the 16-row MFMA kernel depending on where they fall in the launch
-    # (hconv16_kernel.h), so across batch sizes Z agrees to fp32 reassociation, not bitwise
+    # SSRN rows are served by the main launch or by the tap / K-third tail depending on where they fall in the launch
+    # (run_conv), so across batch sizes Z agrees to fp32 reassociation, not bitwise
     assert float((torch.cat((Za, Zb)) - Z).abs().max()) < 1e-5
     m = mx.cpu().numpy()
     dm = np.diff(m, axis=1)
@@ -717,7 +718,7 @@ dist.destroy_process_group()
 def test_two_ranks_share_gpu_gather_equals_single_process(weights, tmp_path):
     """SURVEY 8e end to end on one GPU: two ranks (gloo, both on cuda:0) decode their contiguous slices, copy the results into
     pinned host buffers and meet on rank 0's host; (Y, trajectory) must be bitwise the single-process result, Z to the 1e-5 of
-    the SSRN row-split (hconv16_kernel.h).  Both sides decode with one launch per layer: team kernels of two processes on ONE GPU hold compute units
+    the SSRN row-split (run_conv's tail forms).  Both sides decode with one launch per layer: team kernels of two processes on ONE GPU hold compute units
     the other process's teams wait for (the driver's ranks have a GPU each; inside a process the device lease serialises decodes), and a decode repeated in
     the per-layer form is equal to the team form to 3e-6, not bitwise."""
     import subprocess
