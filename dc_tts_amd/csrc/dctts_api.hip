@@ -66,25 +66,45 @@ hipError_t launch_hconv(const ConvShape& s, const ConvParams& p, hipStream_t str
 }
 
 // The opt-in split-bf16 form (hconv_kernel.h: BF): whole 32-row items, no row tail.  parts = 2: a 64-tile highway layer as two column halves + the finishing pass.
-hipError_t launch_hconv_bf16(const ConvShape& s, const ConvParams& p, hipStream_t stream) {
+// terms = 3: the three-term form (BF = 2) on the [hi | mid | lo] packing -- the same shape classes; ring depth 1 at NT = 4 (a slot is 48 registers), 2 at NT = 2.
+// Where the three-term form's 3 NT weight requests sit among a group's 6 NT MFMAs (hconv_kernel.h: SG for BF = 2), by tools/micro/hconv_lab at 768 items (profiles/r07_hconv_lab.txt):
+// NT = 4: one in front of every second MFMA -- 1600 us (HC_11 halves) / 431 (HC_8) / 335 (C_14) / 189 (C_10) against 1752 / 471 / 358 / 200 where the scheduler is left alone (it sinks the
+// requests behind the group's last six MFMAs) and 1654 / 447 / 347 / 193 with all of them in front of the first 3 NT.  NT = 2 (ring depth 2): left alone -- pinned it is 7 to 23 % slower.
+constexpr int BF3_SG = 2;
+hipError_t launch_hconv_bf16(const ConvShape& s, const ConvParams& p, hipStream_t stream, int terms) {
   if (p.M <= 0) return hipSuccess;
+  if (terms != 2 && terms != 3) return hipErrorInvalidValue;
   const int items = (p.M + 31) / 32;
   if (p.wx) {
     if (s.epi != EPI_C || p.cout != 1025 || p.ntaps != 1 || p.cin_p > 1120) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((hconv_kernel<EPI_C, 4, 8, 2, 1, 0, 1, 1>), dim3(items), dim3(512), 0, stream, p);
+    if (terms == 3) hipLaunchKernelGGL((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 1, 2, BF3_SG>), dim3(items), dim3(512), 0, stream, p);
+    else hipLaunchKernelGGL((hconv_kernel<EPI_C, 4, 8, 2, 1, 0, 1, 1>), dim3(items), dim3(512), 0, stream, p);
     return hipGetLastError();
   }
   if (s.epi == EPI_HC && s.nt == 8 && s.nw == 8) {
     if (!p.raw_out || p.m_base != 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((hconv_kernel<EPI_HC, 4, 8, 2, 1, 2, 0, 1>), dim3(items, 2), dim3(512), 0, stream, p);
+    if (terms == 3) hipLaunchKernelGGL((hconv_kernel<EPI_HC, 4, 8, 1, 1, 2, 0, 2, BF3_SG>), dim3(items, 2), dim3(512), 0, stream, p);
+    else hipLaunchKernelGGL((hconv_kernel<EPI_HC, 4, 8, 2, 1, 2, 0, 1>), dim3(items, 2), dim3(512), 0, stream, p);
     hipError_t e_ = hipGetLastError();
     if (e_ != hipSuccess) return e_;
     hipLaunchKernelGGL(hc_tail_finish_kernel, dim3((p.M + 3) / 4), dim3(256), 0, stream, p, (const float*)p.raw_out, 1);
     return hipGetLastError();
   }
-  if (s.epi == EPI_HC && s.nt == 4 && s.nw == 8) { hipLaunchKernelGGL((hconv_kernel<EPI_HC, 4, 8, 1, 1, 0, 0, 1>), dim3(items), dim3(512), 0, stream, p); return hipGetLastError(); }      // (ring depth 1: 274 against 298 us for HC_8's 768 items, tools/micro/hconv_lab)
-  if (s.epi == EPI_C && s.nt == 4 && s.nw == 8) { hipLaunchKernelGGL((hconv_kernel<EPI_C, 4, 8, 2, 1, 0, 0, 1>), dim3(items), dim3(512), 0, stream, p); return hipGetLastError(); }
-  if (s.epi == EPI_C && s.nt == 2 && s.nw == 8) { hipLaunchKernelGGL((hconv_kernel<EPI_C, 2, 8, 2, 1, 0, 0, 1>), dim3(items), dim3(512), 0, stream, p); return hipGetLastError(); }
+  if (s.epi == EPI_HC && s.nt == 4 && s.nw == 8) {      // (ring depth 1: 274 against 298 us for HC_8's 768 items, tools/micro/hconv_lab)
+    if (terms == 3) hipLaunchKernelGGL((hconv_kernel<EPI_HC, 4, 8, 1, 1, 0, 0, 2, BF3_SG>), dim3(items), dim3(512), 0, stream, p);
+    else hipLaunchKernelGGL((hconv_kernel<EPI_HC, 4, 8, 1, 1, 0, 0, 1>), dim3(items), dim3(512), 0, stream, p);
+    return hipGetLastError();
+  }
+  if (s.epi == EPI_C && s.nt == 4 && s.nw == 8) {
+    if (terms == 3) hipLaunchKernelGGL((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 0, 2, BF3_SG>), dim3(items), dim3(512), 0, stream, p);
+    else hipLaunchKernelGGL((hconv_kernel<EPI_C, 4, 8, 2, 1, 0, 0, 1>), dim3(items), dim3(512), 0, stream, p);
+    return hipGetLastError();
+  }
+  if (s.epi == EPI_C && s.nt == 2 && s.nw == 8) {
+    if (terms == 3) hipLaunchKernelGGL((hconv_kernel<EPI_C, 2, 8, 2, 1, 0, 0, 2>), dim3(items), dim3(512), 0, stream, p);
+    else hipLaunchKernelGGL((hconv_kernel<EPI_C, 2, 8, 2, 1, 0, 0, 1>), dim3(items), dim3(512), 0, stream, p);
+    return hipGetLastError();
+  }
   return hipErrorInvalidConfiguration;
 }
 
@@ -303,6 +323,7 @@ struct dctts_ctx {
   int n_cu = 256;                      // CUs of the device (hipDeviceProp_t::multiProcessorCount)
   int bf16_packed = 0;                 // dctts_set_split_bf16 before finalize: 1 = SSRN's layers carry the bf16 packing, 2 = TextEnc's as well
   int bf16_mode = 0;                   // ... and what runs: 0 = exact fp32 (default), 1 = SSRN on the split-bf16 form, 2 = SSRN + TextEnc
+  int bf16_terms = 2;                  // dctts_set_split_bf16_terms: 2 = hi.hi + hi.mid + mid.hi, 3 = the six products of three terms; fixed at finalize (it decides the packing)
   int pack_bf16_now = 0;               // (set while finalize builds a network whose layers get the packing)
   bool bf_te = false;                  // ... and the network is TextEnc (scratch of the TextEnc group: run_conv)
   bool bf_now = false;                 // set by the TextEnc / SSRN drivers around their run_conv calls when the split-bf16 form is selected for that network
@@ -421,6 +442,7 @@ static std::vector<float> pack_bw(const std::function<float(int, int, int)>& W, 
 }
 // The split-bf16 packing (hconv_kernel.h: BF): [tile][16-k group][hi | mid][lane][8 bf16]; lane l, element e <- k = 16 g + 8 (l >> 5) + e, column l & 31 of the tile.
 // hi = bf16(w), mid = bf16(w - hi), both round-to-nearest-even.  Returned as floats (two bf16 per float) so that it travels through upload().
+// terms = 3 (dctts_set_split_bf16_terms): [tile][16-k group][hi | mid | lo][lane][8 bf16] with lo = bf16(w - hi - mid); both subtractions are exact in fp32.
 static uint16_t f2bf16(float f) {
   uint32_t u; memcpy(&u, &f, 4);
   if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
@@ -428,9 +450,9 @@ static uint16_t f2bf16(float f) {
   return (uint16_t)(u >> 16);
 }
 static float bf16_2f(uint16_t h) { const uint32_t u = (uint32_t)h << 16; float f; memcpy(&f, &u, 4); return f; }
-static std::vector<float> pack_bw_bf16(const std::function<float(int, int, int)>& W, int ntaps, int cin_real, int cin_p, int tiles, int cout, bool hc) {
+static std::vector<float> pack_bw_bf16(const std::function<float(int, int, int)>& W, int ntaps, int cin_real, int cin_p, int tiles, int cout, bool hc, int terms) {
   const int KG = ntaps * cin_p / 16;
-  std::vector<uint16_t> out((size_t)tiles * KG * 2 * 64 * 8, 0);
+  std::vector<uint16_t> out((size_t)tiles * KG * terms * 64 * 8, 0);
   for (int gt = 0; gt < tiles; ++gt)
     for (int kg = 0; kg < KG; ++kg)
       for (int l = 0; l < 64; ++l) {
@@ -443,9 +465,10 @@ static std::vector<float> pack_bw_bf16(const std::function<float(int, int, int)>
           if (cc >= cin_real) continue;
           const float w = W(tap, cc, col);
           const uint16_t hi = f2bf16(w), mid = f2bf16(w - bf16_2f(hi));
-          const size_t base = (((size_t)gt * KG + kg) * 2) * 64 * 8;
+          const size_t base = (((size_t)gt * KG + kg) * terms) * 64 * 8;
           out[base + (size_t)l * 8 + e] = hi;
           out[base + 64 * 8 + (size_t)l * 8 + e] = mid;
+          if (terms == 3) out[base + 2 * 64 * 8 + (size_t)l * 8 + e] = f2bf16(w - bf16_2f(hi) - bf16_2f(mid));
         }
       }
   std::vector<float> f(out.size() / 2);
@@ -477,8 +500,8 @@ static int make_C(dctts_ctx* c, const std::string& scope, int cin_real, int cin_
     L->row_tail = true;
   }
   if (c->pack_bf16_now) {
-    if (cout == 1025) CHK(upload(c, pack_bw_bf16(W, 1, cin_real, L->cin_p, 32, 1024, false), &L->wpb));      // + wxcol below: the last column stays an fp32 dot product
-    else CHK(upload(c, pack_bw_bf16(W, 1, cin_real, L->cin_p, L->shape.nt * L->shape.nw, cout, false), &L->wpb));
+    if (cout == 1025) CHK(upload(c, pack_bw_bf16(W, 1, cin_real, L->cin_p, 32, 1024, false, c->bf16_terms), &L->wpb));      // + wxcol below: the last column stays an fp32 dot product
+    else CHK(upload(c, pack_bw_bf16(W, 1, cin_real, L->cin_p, L->shape.nt * L->shape.nw, cout, false, c->bf16_terms), &L->wpb));
   }
   if (((tail && c->ssrn_xc) || c->pack_bf16_now) && cout == 1025 && L->cin_p <= 1120) {
     if (tail && c->ssrn_xc) CHK(upload(c, pack_bw(W, 1, cin_real, L->cin_p, 32, 1024, false, 32), &L->wpx));
@@ -518,7 +541,7 @@ static int make_HC(dctts_ctx* c, const std::string& scope, int C, int k, int rat
     L->shape16 = pick_shape16(EPI_HC, C);
     L->row_tail = true;
   }
-  if (c->pack_bf16_now) CHK(upload(c, pack_bw_bf16(W, k, C, L->cin_p, L->shape.nt * L->shape.nw, C, true), &L->wpb));
+  if (c->pack_bf16_now) CHK(upload(c, pack_bw_bf16(W, k, C, L->cin_p, L->shape.nt * L->shape.nw, C, true, c->bf16_terms), &L->wpb));
   L->hc = true;
   CHK(upload(c, b->v, &L->bias));
   CHK(upload(c, g1->v, &L->g1)); CHK(upload(c, b1->v, &L->b1));
@@ -549,7 +572,7 @@ static int make_D(dctts_ctx* c, const std::string& scope, int C, DevLayer* even,
       return kv[((size_t)j * C + col) * C + cc];          // kernel[0][j][out][in]
     };
     CHK(upload(c, pack_b(W, L->ntaps, C, L->cin_p, L->shape, C, false), &L->wp));
-    if (c->pack_bf16_now) CHK(upload(c, pack_bw_bf16(W, L->ntaps, C, L->cin_p, L->shape.nt * L->shape.nw, C, false), &L->wpb));
+    if (c->pack_bf16_now) CHK(upload(c, pack_bw_bf16(W, L->ntaps, C, L->cin_p, L->shape.nt * L->shape.nw, C, false, c->bf16_terms), &L->wpb));
     L->bias = bias; L->g1 = g; L->b1 = bb;
   }
   return 0;
@@ -904,7 +927,7 @@ static int run_conv(dctts_ctx* c, const DevLayer& L, const View& in, const int* 
       if (need > *fl) CHK(grow_scratch(c, buf, fl, need));
       p.m_base = 0; p.raw_out = *buf; p.raw_ld = 2 * L.cout;
     }
-    HIPCHK(launch_hconv_bf16(L.shape, p, st));
+    HIPCHK(launch_hconv_bf16(L.shape, p, st, c->bf16_terms));
     c->conv_forms[DCTTS_FORM_SPLIT_BF16] += p.M;
     if (prof) { HIPCHK(hipEventRecord(e1, st)); c->prof_ev.emplace_back(e0, e1); c->prof_cnt.push_back(1); c->prof_rows += p.M; }
     return 0;
@@ -1047,6 +1070,14 @@ extern "C" int dctts_set_split_bf16(dctts_ctx* c, int mode) {
   if (!c->finalized) { c->bf16_packed = mode; c->bf16_mode = mode; return 0; }      // before dctts_weights_finalize: the level that gets packed (and runs)
   if (mode > c->bf16_packed) return fail(DCTTS_ERR_STATE, "split-bf16: this level was not requested before dctts_weights_finalize (the bf16 weight packing does not exist)");
   c->bf16_mode = mode;
+  return 0;
+}
+
+extern "C" int dctts_set_split_bf16_terms(dctts_ctx* c, int terms) {
+  if (!c || (terms != 2 && terms != 3)) return fail(DCTTS_ERR_ARG, "split-bf16 terms: 2 (hi.hi + hi.mid + mid.hi) or 3 (six products of hi + mid + lo)");
+  std::lock_guard<std::recursive_mutex> lk(c->mu);
+  if (c->finalized && terms != c->bf16_terms) return fail(DCTTS_ERR_STATE, "split-bf16: this number of terms was not requested before dctts_weights_finalize (the bf16 weight packing has the other form)");
+  c->bf16_terms = terms;
   return 0;
 }
 

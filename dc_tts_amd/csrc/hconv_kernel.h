@@ -41,6 +41,22 @@ __device__ __forceinline__ void split_bf16_pair(float x0, float x1, unsigned& hi
   const bf16x2_t m = __builtin_convertvector((f32x2_t){x0 - h0, x1 - h1}, bf16x2_t);
   mid = __builtin_bit_cast(unsigned, m);
 }
+// Three-term split (opt-in: dctts_set_split_bf16_terms(ctx, 3); hconv_kernel<BF = 2>).  x = hi + mid + lo EXACTLY: x - hi has at most 16 significant bits, mid takes the
+// upper 8 of them, so lo = bf16(x - hi - mid) is exact as well (both subtractions are exact in fp32; only a remainder below the bf16 subnormal range is lost).  Six
+// products are accumulated, small terms first:  lo.hi + hi.lo + mid.mid + mid.hi + hi.mid + hi.hi;  what is dropped, mid.lo + lo.mid + lo.lo, is <= ~2^-26 of |x||w|
+// per product -- below one fp32 accumulate rounding (2^-24) -- and the accumulator is rounded 6 times per 16 k where the fp32 instruction rounds it 8 times.
+// 6 x 32 matrix cycles per 16 k against 3 x 32 (two terms) and 8 x 64 (fp32).
+// (The four subtractions are single v_sub_f32: written out so that the pairs are never fused into packed fp32 instructions.)
+__device__ __forceinline__ float split_sub_f32(float a, float b) { float d; asm("v_sub_f32_e32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b)); return d; }
+__device__ __forceinline__ void split_bf16_pair3(float x0, float x1, unsigned& hi, unsigned& mid, unsigned& lo) {
+  const bf16x2_t h = __builtin_convertvector((f32x2_t){x0, x1}, bf16x2_t);
+  hi = __builtin_bit_cast(unsigned, h);
+  const float r0 = split_sub_f32(x0, __uint_as_float(hi << 16)), r1 = split_sub_f32(x1, __uint_as_float(hi & 0xffff0000u));
+  const bf16x2_t m = __builtin_convertvector((f32x2_t){r0, r1}, bf16x2_t);
+  mid = __builtin_bit_cast(unsigned, m);
+  const bf16x2_t l = __builtin_convertvector((f32x2_t){split_sub_f32(r0, __uint_as_float(mid << 16)), split_sub_f32(r1, __uint_as_float(mid & 0xffff0000u))}, bf16x2_t);
+  lo = __builtin_bit_cast(unsigned, l);
+}
 
 enum { EPI_C = 0, EPI_HC = 1 };
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_SIGMOID = 2 };
@@ -131,6 +147,11 @@ __device__ __forceinline__ float half_sum32(float v) {
 //     v_mfma_f32_32x32x16_bf16 wants its B operand; the A operand is the same 8 consecutive channels of row l & 31 out of the fp32 LDS tile.  The
 //     accumulators come out in the fp32 instruction's layout, so prologue, statistics and epilogue are shared.  NT <= 4 (a 16-k group of weights is
 //     8 NT registers per ring slot); the 64-tile layers run as two column halves (RAW = 2) + the finishing pass.
+//   * BF = 2 (opt-in, dctts_set_split_bf16_terms(ctx, 3)): three bf16 terms per operand, six MFMAs per tile and 16-k group, small products first (above); p.wp points at
+//     [tile][16-k group][hi | mid | lo][lane][8 bf16], 192 fragments per group.  A ring slot is 12 NT registers, so the ring is one group deep at NT = 4 (48 in the ring,
+//     48 in flight, 64 accumulators) and two deep only at NT = 2.  SG places the group's 3 NT weight requests: 0 = the compiler's scheduler (it sinks them behind the
+//     group's LAST six MFMAs, so the next group waits for them), 1 = one in front of each of the first 3 NT MFMAs, 2 = one in front of every second MFMA (NT = 4, hconv_lab,
+//     768 items: HC_8 472 / 453 / 436 us for SG = 0 / 1 / 2, fp32 635; at NT = 2 the pins cost 7-23 %).  Same staging, barrier, prologue, statistics and epilogue as BF = 1.
 //   * SG (round 6): where the NT + 1 requests of a k-group (NT weight fragments, the next A fragment) sit among its 4 NT MFMAs.  0: wherever the compiler's scheduler
 //     puts them (rounds 1-5; a PIN in front of the MFMAs was 27 % slower in round 3).  1 / 2: spread with sched_group_barrier -- one MFMA, the LDS read, then one
 //     weight request behind every three (1) / four (2) MFMAs.  tools/micro/mfma_feed_lab.hip: a wave issues in order, so requests clustered in front of a k-group's
@@ -140,6 +161,8 @@ template <int EPI, int NT, int NW, int BD = 1, int SB = 0, int RAW = 0, int XC =
 __global__ void __launch_bounds__(NW * 64, (XC == 2) ? 4 : ((NW == 4 && NT == 8 && RAW == 0) ? 2 : 1)) hconv_kernel(const ConvParams p) {      // (XC = 2: the same with registers capped for two workgroups per CU)
   static_assert(XC == 0 || (EPI == EPI_C && RAW == 0 && NW == 8), "the extra column rides in the fused k = 1 form: 8 waves x 4 rows");
   static_assert(BF == 0 || (RAW != 1 && NT <= 4 && (BD == 1 || BD == 2)), "split-bf16: whole-K items, at most four tiles per wave, ring rotated by the two groups of a chunk");
+  static_assert(BF >= 0 && BF <= 2 && (BF != 2 || BD == 1 || NT <= 2), "three-term split-bf16: a ring slot is 12 NT registers -- two slots only at NT <= 2");
+  constexpr int BFF = (BF == 2) ? 192 : 128;      // BF: 16-byte fragments per (tile, 16-k group)
   constexpr bool KPART = (RAW == 1);        // this workgroup contracts a PART of K (grid y = part)
   constexpr bool CPART = (RAW == 2);        // this workgroup owns a PART of the columns (grid y = part)
   constexpr int LDA = 36;
@@ -221,11 +244,11 @@ __global__ void __launch_bounds__(NW * 64, (XC == 2) ? 4 : ((NW == 4 && NT == 8 
   for (int i = 0; i < NT; ++i)
     wq[i] = reinterpret_cast<const float4*>(p.wp) + ((long)(wv * NT + i) * KGT + kg0) * 64 + (SB ? 0 : lane);
   const int wl = SB ? lane : 0;
-  // BF: [tile][16-k group][hi | mid][lane] of 16-byte fragments; nch * 2 groups per tile (whole-K items only)
+  // BF: [tile][16-k group][hi | mid (| lo)][lane] of 16-byte fragments; nch * 2 groups per tile (whole-K items only)
   const uint4* wb[NT];
 #pragma unroll
   for (int i = 0; i < NT; ++i)
-    wb[i] = reinterpret_cast<const uint4*>(p.wp) + (long)(wv * NT + i) * (p.ntaps * cpt * 2) * 128 + (SB ? 0 : lane);
+    wb[i] = reinterpret_cast<const uint4*>(p.wp) + (long)(wv * NT + i) * (p.ntaps * cpt * 2) * BFF + (SB ? 0 : lane);
   const int KG16 = nch * 2;
 
   // channel of tile i inside its layer-norm group; the bias is the accumulators' initial value (columns beyond C: zero weights, zero bias -> exactly 0)
@@ -248,6 +271,7 @@ __global__ void __launch_bounds__(NW * 64, (XC == 2) ? 4 : ((NW == 4 && NT == 8 
   float4 a1 = load_next(aok1);
   float4 bq[BD][NT];                       // fragments of k-groups kg .. kg + BD - 1
   uint4 bh[BD][NT], bm[BD][NT];            // BF: the hi / mid fragments of 16-k groups g .. g + BD - 1
+  uint4 bl[BD][(BF == 2) ? NT : 1];        // BF = 2: ... and the lo fragments
   if constexpr (!BF) {
 #pragma unroll
     for (int d = 0; d < BD; ++d)
@@ -257,7 +281,10 @@ __global__ void __launch_bounds__(NW * 64, (XC == 2) ? 4 : ((NW == 4 && NT == 8 
 #pragma unroll
     for (int d = 0; d < BD; ++d)
 #pragma unroll
-      for (int i = 0; i < NT; ++i) { const int g = (d < KG16 ? d : KG16 - 1) * 128 + wl; bh[d][i] = wb[i][g]; bm[d][i] = wb[i][g + 64]; }
+      for (int i = 0; i < NT; ++i) {
+        const int g = (d < KG16 ? d : KG16 - 1) * BFF + wl; bh[d][i] = wb[i][g]; bm[d][i] = wb[i][g + 64];
+        if constexpr (BF == 2) bl[d][i] = wb[i][g + 128];
+      }
   }
   if (!aok) a0 = make_float4(0.f, 0.f, 0.f, 0.f);
   if (!aok1) a1 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -296,9 +323,37 @@ __global__ void __launch_bounds__(NW * 64, (XC == 2) ? 4 : ((NW == 4 && NT == 8 
         }
         const float* nx = (q == 0) ? &Ab[aoffb + 16] : &An[aoffb];
         const float4 an0 = *reinterpret_cast<const float4*>(nx), an1 = *reinterpret_cast<const float4*>(nx + 4);
-        uint4 bhn[NT], bmn[NT];
+        uint4 bhn[NT], bmn[NT], bln[(BF == 2) ? NT : 1];
 #pragma unroll
-        for (int i = 0; i < NT; ++i) { bhn[i] = wb[i][kgn * 128 + wl]; bmn[i] = wb[i][kgn * 128 + 64 + wl]; }
+        for (int i = 0; i < NT; ++i) {
+          bhn[i] = wb[i][kgn * BFF + wl]; bmn[i] = wb[i][kgn * BFF + 64 + wl];
+          if constexpr (BF == 2) bln[i] = wb[i][kgn * BFF + 128 + wl];
+        }
+        if constexpr (BF == 2) {
+          uint4 ah, am, al;
+          split_bf16_pair3(af0.x, af0.y, ah.x, am.x, al.x); split_bf16_pair3(af0.z, af0.w, ah.y, am.y, al.y);
+          split_bf16_pair3(af1.x, af1.y, ah.z, am.z, al.z); split_bf16_pair3(af1.z, af1.w, ah.w, am.w, al.w);
+          const bf16x8_t ahv = __builtin_bit_cast(bf16x8_t, ah), amv = __builtin_bit_cast(bf16x8_t, am), alv = __builtin_bit_cast(bf16x8_t, al);
+          // small products first: lo.hi, hi.lo, mid.mid (each <= 2^-16 |x||w|), then mid.hi, hi.mid (<= 2^-8), then hi.hi; NT independent accumulators between two uses of one
+#pragma unroll
+          for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(alv, __builtin_bit_cast(bf16x8_t, bh[0][i]), acc[i], 0, 0, 0);
+#pragma unroll
+          for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahv, __builtin_bit_cast(bf16x8_t, bl[0][i]), acc[i], 0, 0, 0);
+#pragma unroll
+          for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(amv, __builtin_bit_cast(bf16x8_t, bm[0][i]), acc[i], 0, 0, 0);
+#pragma unroll
+          for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(amv, __builtin_bit_cast(bf16x8_t, bh[0][i]), acc[i], 0, 0, 0);
+#pragma unroll
+          for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahv, __builtin_bit_cast(bf16x8_t, bm[0][i]), acc[i], 0, 0, 0);
+#pragma unroll
+          for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahv, __builtin_bit_cast(bf16x8_t, bh[0][i]), acc[i], 0, 0, 0);
+#pragma unroll
+          for (int i = 0; i < NT; ++i) {
+#pragma unroll
+            for (int d = 0; d + 1 < BD; ++d) bl[d][i] = bl[d + 1][i];
+            bl[BD - 1][i] = bln[i];
+          }
+        } else {
         uint4 ah, am;
         split_bf16_pair(af0.x, af0.y, ah.x, am.x); split_bf16_pair(af0.z, af0.w, ah.y, am.y);
         split_bf16_pair(af1.x, af1.y, ah.z, am.z); split_bf16_pair(af1.z, af1.w, ah.w, am.w);
@@ -309,6 +364,7 @@ __global__ void __launch_bounds__(NW * 64, (XC == 2) ? 4 : ((NW == 4 && NT == 8 
         for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ahv, __builtin_bit_cast(bf16x8_t, bm[0][i]), acc[i], 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < NT; ++i) acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(amv, __builtin_bit_cast(bf16x8_t, bh[0][i]), acc[i], 0, 0, 0);
+        }
 #pragma unroll
         for (int i = 0; i < NT; ++i) {
 #pragma unroll
@@ -316,6 +372,17 @@ __global__ void __launch_bounds__(NW * 64, (XC == 2) ? 4 : ((NW == 4 && NT == 8 
           bh[BD - 1][i] = bhn[i]; bm[BD - 1][i] = bmn[i];
         }
         af0 = an0; af1 = an1;
+        if constexpr (BF == 2 && SG == 1) {       // the 3 NT weight requests in front of the group's first 3 NT MFMAs, one each (left alone the scheduler sinks them behind the LAST six)
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+#pragma unroll
+          for (int i = 0; i < 3 * NT; ++i) { __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); }
+          __builtin_amdgcn_sched_group_barrier(0x008, 3 * NT - 1, 0);
+        } else if constexpr (BF == 2 && SG == 2) {      // ... spread over the whole group: one request in front of every second MFMA
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+#pragma unroll
+          for (int i = 0; i + 1 < 3 * NT; ++i) { __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); }
+          __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+        }
       }
     } else {
 #pragma unroll

@@ -39,7 +39,7 @@ class Engine:
     """Owns the device-resident packed weights and workspaces for one GPU."""
 
     def __init__(self, weights: Dict[str, np.ndarray], hp: Hyperparams = _hp, device: Optional[int] = None,
-                 decode_graph: bool = False, keep_weights: bool = True, split_bf16: int = 0):
+                 decode_graph: bool = False, keep_weights: bool = True, split_bf16: int = 0, split_bf16_terms: int = 2):
         if not torch.cuda.is_available():
             raise DcttsError("dc_tts_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         self.lib = _lib.load()
@@ -54,8 +54,11 @@ class Engine:
         self._h = h
         # split_bf16 (OPT-IN, default 0 = exact fp32): 1 = SSRN, 2 = SSRN + TextEnc contract on the bf16 matrix pipe from split operands (dctts_set_split_bf16);
         # the level given here is what gets packed at upload, set_split_bf16() then selects any level up to it
+        # split_bf16_terms: 2 (default) = hi.hi + hi.mid + mid.hi; 3 = six products of three bf16 terms, fp32-grade error (dctts_set_split_bf16_terms); fixed at upload
         if split_bf16:
             self._ok(self.lib.dctts_set_split_bf16(self._h, int(split_bf16)))
+        if split_bf16_terms != 2:
+            self._ok(self.lib.dctts_set_split_bf16_terms(self._h, int(split_bf16_terms)))
         for name, arr in weights.items():
             a = np.ascontiguousarray(arr, dtype=np.float32)
             shape = (ctypes.c_int64 * a.ndim)(*a.shape)
@@ -85,6 +88,10 @@ class Engine:
     def set_split_bf16(self, mode: int):
         """0: exact fp32 (default); 1: SSRN, 2: SSRN + TextEnc on split-bf16 operands -- only levels up to the one the Engine was created with."""
         self._ok(self.lib.dctts_set_split_bf16(self._h, int(mode)))
+
+    def set_split_bf16_terms(self, terms: int):
+        """2 or 3 bf16 terms per operand in the split-bf16 networks; after upload only the value the Engine was created with is accepted."""
+        self._ok(self.lib.dctts_set_split_bf16_terms(self._h, int(terms)))
 
     def set_decode_graph(self, enable):
         """False/0 (default): eager launches; True/1: the side stream's work as one hipGraph per frame (measured slower)."""

@@ -146,6 +146,16 @@ size_t dctts_device_bytes(const dctts_ctx* ctx);
  * sequence.  Measured error against the float64 oracle: tests/test_gpu_parity.py::test_split_bf16_*, DESIGN.md section 11. */
 int dctts_set_split_bf16(dctts_ctx* ctx, int mode);
 
+/* Which arithmetic the split-bf16 networks run (dctts_set_split_bf16 says WHICH networks; the decode never runs in either).  terms = 2 (default): the form above.
+ * terms = 3: every weight and activation is written as hi + mid + lo, three bf16 terms (round-to-nearest-even; lo = bf16(x - hi - mid) from the exact remainder, so the
+ * three terms carry all 24 mantissa bits and x = hi + mid + lo exactly), and a product is accumulated in fp32 from SIX matrix instructions, small products first:
+ * lo.hi + hi.lo + mid.mid + mid.hi + hi.mid + hi.hi.  Every bf16 x bf16 product is exact in fp32; what is dropped, mid.lo + lo.mid + lo.lo, is <= ~2^-26 of |x||w|
+ * per product, below one fp32 accumulate rounding (2^-24), and the accumulator is rounded 6 times per 16 k against 8 in the fp32 form: fp32-grade error at
+ * 6 x 32 matrix cycles per 16 k against 8 x 64 (fp32) and 3 x 32 (two terms).  The weights' packing has three fragments per group instead of two, so the value in force
+ * at dctts_weights_finalize is the one the context keeps: afterwards a different value is DCTTS_ERR_STATE (the same value is accepted).  Anything but 2 or 3 is
+ * DCTTS_ERR_ARG.  Measured error and time: tests/test_gpu_split_bf16_terms.py, DESIGN.md section 11. */
+int dctts_set_split_bf16_terms(dctts_ctx* ctx, int terms);
+
 /* Workspaces and the decode's device tables are cached per geometry (B, T, N) and only grow: a serving loop that alternates
  * between batch shapes pays an allocation the first time a shape is seen and nothing afterwards (no hipDeviceSynchronize, no
  * hipFree on a shape change).  When the cached workspaces exceed `bytes` (default 96 GiB of the 288 GB) the next call drops

@@ -1,6 +1,6 @@
 // hconv_lab.hip -- standalone timing lab for the SSRN / TextEnc throughput kernel.  Not product code, and since round 5 it holds NO kernel of its own: every variant
 // is an instantiation of the PRODUCT template dc_tts_amd/csrc/hconv_kernel.h (weight ring depth BD, scalar tile bases SB, the extra-column form XC, the opt-in
-// split-bf16 contraction BF) on the layer shapes of networks.py:214-292 at the bench batch (B = 32 -> 26 880 rows at 4T).  (Rounds 3-4 kept 1 267 lines of copied loop /
+// split-bf16 contraction BF, two terms = 1 / three terms = 2) on the layer shapes of networks.py:214-292 at the bench batch (B = 32 -> 26 880 rows at 4T).  (Rounds 3-4 kept 1 267 lines of copied loop /
 // epilogue variants and ablations beside it -- tools/micro/hconv_lab_kernels.h, deleted: git history; what they measured is in profiles/r03_hconv_lab.txt and
 // DESIGN.md section 4.)  Protocol: every variant is timed IN TURN over `reps` rounds with a 1 GB cache-thrashing pass in front of every timed launch, median reported --
 // repeating one kernel back to back keeps its weights cache-resident and re-ranks the variants.
@@ -55,16 +55,17 @@ int main(int argc, char** argv) {
     const size_t nin = (size_t)B * rows * stride_in, nout = (size_t)B * rows * stride_out;
     const int tiles = (S.epi == EPI_HC ? 2 : 1) * ((S.cout + 31) / 32), K = S.ntaps * S.cin_p;
     const size_t nw = (size_t)tiles * K * 32;                 // floats of the fp32 packing = bytes/4 of the bf16 (hi, mid) packing: the same buffer serves both (timing only for BF)
+    const size_t nwb = nw + nw / 2;                           // ... and 1.5 x that for the three-term (hi, mid, lo) packing of BF = 2: the buffer is allocated at this size
     uint64_t seed = 1234 + si;
     std::vector<float> h(nin);
     for (auto& v : h) v = frand(seed);
     float *in, *out, *ref, *wp, *wx, *raw, *bias, *g1, *b1, *g2, *b2;
     CK(hipMalloc(&in, nin * 4)); CK(hipMemcpy(in, h.data(), nin * 4, hipMemcpyHostToDevice));
     CK(hipMalloc(&out, nout * 4)); CK(hipMalloc(&ref, nout * 4)); CK(hipMalloc(&raw, (size_t)B * R * 2 * S.cout * 4));
-    std::vector<float> w(nw);
+    std::vector<float> w(nwb);
     const float ws = 1.0f / std::sqrt((float)(S.ntaps * S.cin));
     for (auto& v : w) v = frand(seed) * ws;
-    CK(hipMalloc(&wp, nw * 4)); CK(hipMemcpy(wp, w.data(), nw * 4, hipMemcpyHostToDevice));
+    CK(hipMalloc(&wp, nwb * 4)); CK(hipMemcpy(wp, w.data(), nwb * 4, hipMemcpyHostToDevice));
     std::vector<float> v1(4096);
     auto up = [&](float** d, float base, float amp) { for (auto& v : v1) v = base + amp * frand(seed); CK(hipMalloc(d, 4096 * 4)); CK(hipMemcpy(*d, v1.data(), 4096 * 4, hipMemcpyHostToDevice)); };
     up(&bias, 0.f, 0.1f); up(&g1, 1.f, 0.1f); up(&b1, 0.f, 0.1f); up(&g2, 1.f, 0.1f); up(&b2, 0.f, 0.1f); up(&wx, 0.f, ws);
@@ -89,6 +90,12 @@ int main(int argc, char** argv) {
         RUN((hconv_kernel<EPI_HC, 8, 8, 1, 0, 0, 0, 0, 3>), 512, 1, "SB=0 SG=3 (every two, first half)", true, )
         RUN((hconv_kernel<EPI_HC, 8, 8, 2, 0, 0, 0, 0, 1>), 512, 1, "BD=2 SB=0 SG=1", true, )
         RUN((hconv_kernel<EPI_HC, 4, 8, 2, 1, 2, 0, 1>), 512, 2, "split-bf16: two column halves (pre-norm values to HBM; + the finishing pass, not timed)", false, q.raw_out = raw; q.raw_ld = 2 * q.cout)
+        RUN((hconv_kernel<EPI_HC, 4, 8, 1, 1, 2, 0, 2>), 512, 2, "three-term split-bf16: two column halves, BD=1", false, q.raw_out = raw; q.raw_ld = 2 * q.cout)
+        RUN((hconv_kernel<EPI_HC, 4, 8, 1, 1, 2, 0, 2, 1>), 512, 2, "three-term split-bf16: two column halves, BD=1 SG=1 (a request in front of each of the first 3 NT MFMAs)", false, q.raw_out = raw; q.raw_ld = 2 * q.cout)
+        RUN((hconv_kernel<EPI_HC, 4, 8, 1, 1, 2, 0, 2, 2>), 512, 2, "three-term split-bf16: two column halves, BD=1 SG=2 (a request in front of every second MFMA)", false, q.raw_out = raw; q.raw_ld = 2 * q.cout)
+        RUN((hconv_kernel<EPI_HC, 2, 8, 2, 1, 2, 0, 2>), 512, 4, "three-term split-bf16: four column quarters (NT=2), BD=2", false, q.raw_out = raw; q.raw_ld = 2 * q.cout)
+        RUN((hconv_kernel<EPI_HC, 2, 8, 2, 1, 2, 0, 2, 1>), 512, 4, "three-term split-bf16: four column quarters (NT=2), BD=2 SG=1 (a request in front of each of the first 3 NT MFMAs)", false, q.raw_out = raw; q.raw_ld = 2 * q.cout)
+        RUN((hconv_kernel<EPI_HC, 2, 8, 2, 1, 2, 0, 2, 2>), 512, 4, "three-term split-bf16: four column quarters (NT=2), BD=2 SG=2 (a request in front of every second MFMA)", false, q.raw_out = raw; q.raw_ld = 2 * q.cout)
       } else if (si == 1) {
         RUN((hconv_kernel<EPI_HC, 4, 8, 2, 0>), 512, 1, "production hconv_kernel<HC,4,8,BD=2,SB=0>", false, q.out = ref)
         RUN((hconv_kernel<EPI_HC, 4, 8, 1, 1>), 512, 1, "BD=1 SB=1", true, )
@@ -103,6 +110,10 @@ int main(int argc, char** argv) {
         RUN((hconv_kernel<EPI_HC, 4, 8, 4, 1, 0, 0, 0, 1>), 512, 1, "BD=4 SB=1 SG=1", true, )
         RUN((hconv_kernel<EPI_HC, 4, 8, 2, 1, 0, 0, 1>), 512, 1, "split-bf16 BD=2", false, )
         RUN((hconv_kernel<EPI_HC, 4, 8, 1, 1, 0, 0, 1>), 512, 1, "split-bf16 BD=1", false, )
+        RUN((hconv_kernel<EPI_HC, 4, 8, 1, 1, 0, 0, 2>), 512, 1, "three-term split-bf16 BD=1", false, )
+        RUN((hconv_kernel<EPI_HC, 4, 8, 1, 1, 0, 0, 2, 1>), 512, 1, "three-term split-bf16 BD=1 SG=1 (a request in front of each of the first 3 NT MFMAs)", false, )
+        RUN((hconv_kernel<EPI_HC, 4, 8, 1, 1, 0, 0, 2, 2>), 512, 1, "three-term split-bf16 BD=1 SG=2 (a request in front of every second MFMA)", false, )
+        RUN((hconv_kernel<EPI_HC, 4, 8, 1, 0, 0, 0, 2>), 512, 1, "three-term split-bf16 BD=1 SB=0", false, )
       } else if (si == 2) {
         RUN((hconv_kernel<EPI_C, 3, 11, 2, 1>), 704, 1, "rounds 1-4: hconv_kernel<C,3,11,BD=2,SB=1> (33 tiles on 11 waves)", false, q.out = ref)
         RUN((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 2>), 512, 1, "round 5: 8 waves x 4 tiles + column 1024 on the vector ALU, 128 registers (XC=2)", false, q.wx = wx)
@@ -111,6 +122,9 @@ int main(int argc, char** argv) {
         RUN((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 2, 0, 2>), 512, 1, "XC=2 SG=2", false, q.wx = wx)
         RUN((hconv_kernel<EPI_C, 4, 8, 2, 1, 0, 1, 0, 1>), 512, 1, "production (round 6): XC=1 BD=2 SG=1", false, q.wx = wx)
         RUN((hconv_kernel<EPI_C, 4, 8, 2, 1, 0, 1, 1>), 512, 1, "split-bf16 XC BD=2", false, q.wx = wx)
+        RUN((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 1, 2>), 512, 1, "three-term split-bf16 XC BD=1", false, q.wx = wx)
+        RUN((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 1, 2, 1>), 512, 1, "three-term split-bf16 XC BD=1 SG=1 (a request in front of each of the first 3 NT MFMAs)", false, q.wx = wx)
+        RUN((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 1, 2, 2>), 512, 1, "three-term split-bf16 XC BD=1 SG=2 (a request in front of every second MFMA)", false, q.wx = wx)
       } else {
         RUN((hconv_kernel<EPI_C, 4, 8, 1, 1>), 512, 1, "production hconv_kernel<C,4,8,BD=1,SB=1>", false, q.out = ref)
         RUN((hconv_kernel<EPI_C, 4, 8, 2, 1>), 512, 1, "BD=2", true, )
@@ -119,6 +133,9 @@ int main(int argc, char** argv) {
         RUN((hconv_kernel<EPI_C, 4, 8, 2, 1, 0, 0, 0, 1>), 512, 1, "BD=2 SG=1", true, )
         RUN((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 0, 0, 2>), 512, 1, "BD=1 SG=2", true, )
         RUN((hconv_kernel<EPI_C, 4, 8, 2, 1, 0, 0, 1>), 512, 1, "split-bf16 BD=2", false, )
+        RUN((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 0, 2>), 512, 1, "three-term split-bf16 BD=1", false, )
+        RUN((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 0, 2, 1>), 512, 1, "three-term split-bf16 BD=1 SG=1 (a request in front of each of the first 3 NT MFMAs)", false, )
+        RUN((hconv_kernel<EPI_C, 4, 8, 1, 1, 0, 0, 2, 2>), 512, 1, "three-term split-bf16 BD=1 SG=2 (a request in front of every second MFMA)", false, )
       }
       for (auto& v : vars) {
         CK(hipMemset(out, 0, nout * 4));
