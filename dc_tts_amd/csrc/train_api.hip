@@ -10,6 +10,7 @@
 #include "../../include/dctts_hip.h"
 #include "../../include/dctts_train.h"
 #include "train_kernels.h"
+#include "train_gemm3_kernel.h"
 
 using namespace dctts;
 
@@ -31,6 +32,7 @@ struct dctts_train {
   TBuf xp, Hp, dHp, dxp, part, wpart, lpart, wpad, att;
   bool tape_on = false;               // forward passes keep their pre-norm tensors, backward passes consume them in reverse order
   std::vector<TapeEntry> tape; size_t tape_n = 0;
+  int terms = 0;                      // dctts_train_set_split_bf16_terms: 0 = every contraction on gemm_kernel (fp32 MFMA), 3 = on gemm3_kernel (three-term split bf16)
 };
 
 namespace {
@@ -48,36 +50,40 @@ int reserve(TBuf* b, size_t bytes) {
   b->bytes = bytes;
   return 0;
 }
+// every contraction of the training path is launched here: the fp32 kernel, or -- terms == 3 -- the three-term split-bf16 kernel of the same contract
 template <bool TA, bool TB>
-int gemm(hipStream_t st, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int beta,
+int launch_gemm(const dctts_train* t, hipStream_t st, dim3 grid, const GemmParams& p) {
+  if (t->terms == 3) hipLaunchKernelGGL((gemm3_kernel<TA, TB>), grid, dim3(256), 0, st, p);
+  else hipLaunchKernelGGL((gemm_kernel<TA, TB>), grid, dim3(256), 0, st, p);
+  if (hipGetLastError() != hipSuccess) return dctts_set_error(DCTTS_ERR_HIP, "gemm launch failed");
+  return 0;
+}
+template <bool TA, bool TB>
+int gemm(const dctts_train* t, hipStream_t st, const float* A, const float* B, float* C, int M, int N, int K, int lda, int ldb, int ldc, int beta,
          int splits = 1, long zstride = 0, int nseg = 1, long a_ss = 0, long b_ss = 0) {
   GemmParams p{A, B, C, M, N, K, lda, ldb, ldc, beta, K, zstride, 0, 0, 0};
   p.nseg = nseg; p.a_ss = a_ss; p.b_ss = b_ss;
   if (splits > 1) p.kchunk = ((K + splits - 1) / splits + 15) / 16 * 16;
   const int nz = (K + p.kchunk - 1) / p.kchunk;
-  hipLaunchKernelGGL((gemm_kernel<TA, TB>), dim3((N + 127) / 128, (M + 127) / 128, nz), dim3(256), 0, st, p);
-  if (hipGetLastError() != hipSuccess) return dctts_set_error(DCTTS_ERR_HIP, "gemm launch failed");
-  return nz;
+  const int rc = launch_gemm<TA, TB>(t, st, dim3((N + 127) / 128, (M + 127) / 128, nz), p);
+  return rc ? rc : nz;
 }
 // nb GEMMs of the same shape (A + b * a_zs, B + b * b_zs), each split over K: the partial of (b, split) lands at C + (b * nz + split) * zstride; returns nz
 template <bool TA, bool TB>
-int gemm_batched_splitk(hipStream_t st, int nb, const float* A, long a_zs, const float* B, long b_zs, float* C, long zstride,
+int gemm_batched_splitk(const dctts_train* t, hipStream_t st, int nb, const float* A, long a_zs, const float* B, long b_zs, float* C, long zstride,
                         int M, int N, int K, int lda, int ldb, int ldc, int splits) {
   GemmParams p{A, B, C, M, N, K, lda, ldb, ldc, 0, K, zstride, 1, a_zs, b_zs};
   if (splits > 1) p.kchunk = ((K + splits - 1) / splits + 15) / 16 * 16;
   const int nz = (K + p.kchunk - 1) / p.kchunk;
   p.nsplit = nz;
-  hipLaunchKernelGGL((gemm_kernel<TA, TB>), dim3((N + 127) / 128, (M + 127) / 128, nb * nz), dim3(256), 0, st, p);
-  if (hipGetLastError() != hipSuccess) return dctts_set_error(DCTTS_ERR_HIP, "gemm launch failed");
-  return nz;
+  const int rc = launch_gemm<TA, TB>(t, st, dim3((N + 127) / 128, (M + 127) / 128, nb * nz), p);
+  return rc ? rc : nz;
 }
 // nb independent GEMMs of the same shape: A + z * a_zs, B + z * b_zs, C + z * c_zs
 template <bool TA, bool TB>
-int gemm_batched(hipStream_t st, int nb, const float* A, long a_zs, const float* B, long b_zs, float* C, long c_zs, int M, int N, int K, int lda, int ldb, int ldc, int beta) {
+int gemm_batched(const dctts_train* t, hipStream_t st, int nb, const float* A, long a_zs, const float* B, long b_zs, float* C, long c_zs, int M, int N, int K, int lda, int ldb, int ldc, int beta) {
   GemmParams p{A, B, C, M, N, K, lda, ldb, ldc, beta, K, c_zs, 1, a_zs, b_zs};
-  hipLaunchKernelGGL((gemm_kernel<TA, TB>), dim3((N + 127) / 128, (M + 127) / 128, nb), dim3(256), 0, st, p);
-  if (hipGetLastError() != hipSuccess) return dctts_set_error(DCTTS_ERR_HIP, "gemm launch failed");
-  return 0;
+  return launch_gemm<TA, TB>(t, st, dim3((N + 127) / 128, (M + 127) / 128, nb), p);
 }
 }  // namespace
 
@@ -95,6 +101,13 @@ extern "C" int dctts_train_tape(dctts_train* t, int enable) {
   if (!t) TFAIL(DCTTS_ERR_ARG, "null argument");
   t->tape_on = enable != 0;
   t->tape_n = 0;
+  return 0;
+}
+
+extern "C" int dctts_train_set_split_bf16_terms(dctts_train* t, int terms) {
+  if (!t) TFAIL(DCTTS_ERR_ARG, "null argument");
+  if (terms != 0 && terms != 3) TFAIL(DCTTS_ERR_ARG, "train split_bf16_terms: 0 (fp32 MFMA) or 3 (three-term split bf16)");
+  t->terms = terms;
   return 0;
 }
 
@@ -168,7 +181,7 @@ int conv_prenorm(dctts_train* t, hipStream_t st, const ConvGeom& g, const float*
     }
   }
   {   // all taps in one launch: tap j reads x shifted by j * rate rows and kernel[j]
-    const int rc = gemm<false, false>(st, xp, *kp, Hp + (long)g.pr * g.Chp, (int)g.Rv, g.Chp, g.Cinp, g.Cinp, g.Chp, g.Chp, 0,
+    const int rc = gemm<false, false>(t, st, xp, *kp, Hp + (long)g.pr * g.Chp, (int)g.Rv, g.Chp, g.Cinp, g.Cinp, g.Chp, g.Chp, 0,
                                       1, 0, g.k, (long)g.rate * g.Cinp, (long)g.Cinp * g.Chp);
     if (rc < 0) return rc;
   }
@@ -189,12 +202,12 @@ int conv_grads(dctts_train* t, hipStream_t st, const ConvGeom& g, const float* k
   float *xp = (float*)t->xp.p, *dHp = (float*)t->dHp.p, *dxp = (float*)t->dxp.p;
   const long nw = (long)g.Cin * g.Ch;
   {   // the taps as ONE batched split-K launch (tap j = x shifted by j * rate rows against the same dH), one fixed-order sum, one dgrad launch
-    const int nz = gemm_batched_splitk<true, false>(st, g.k, xp, (long)g.rate * g.Cinp, dHp + (long)g.pr * g.Chp, 0, (float*)t->wpart.p, nw,
+    const int nz = gemm_batched_splitk<true, false>(t, st, g.k, xp, (long)g.rate * g.Cinp, dHp + (long)g.pr * g.Chp, 0, (float*)t->wpart.p, nw,
                                                     g.Cin, g.Ch, (int)g.Rv, g.Cinp, g.Chp, g.Ch, g.splits());
     if (nz < 0) return nz;
     hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((nw + 255) / 256), g.k), dim3(256), 0, st, (const float*)t->wpart.p, nz, nw, nw, dkernel);
     THIP(hipGetLastError());
-    const int rc = gemm<false, true>(st, dHp + (long)(g.pl + g.pr) * g.Chp, kp, dxp + (long)g.pl * g.Cinp, (int)g.Rv, g.Cinp, g.Chp, g.Chp, g.Chp, g.Cinp, 1,      // += : the row kernel left the direct part of dx there
+    const int rc = gemm<false, true>(t, st, dHp + (long)(g.pl + g.pr) * g.Chp, kp, dxp + (long)g.pl * g.Cinp, (int)g.Rv, g.Cinp, g.Chp, g.Chp, g.Chp, g.Cinp, 1,      // += : the row kernel left the direct part of dx there
                                      1, 0, g.k, -(long)g.rate * g.Chp, (long)g.Cinp * g.Chp);
     if (rc < 0) return rc;
   }
@@ -302,9 +315,9 @@ extern "C" int dctts_train_conv1d_transpose_backward(dctts_train* t, const float
   const int M = (int)(R - 1);                       // flat rows r = 1 .. R - 1
   int rc;
   // pre-norm rows (without bias): even rows 2r, odd rows 2r + 1
-  if ((rc = gemm<false, true>(st, xp + Cin, W0, Hp + 2L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 0)) < 0) return rc;
-  if ((rc = gemm<false, true>(st, xp, W2, Hp + 2L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 1)) < 0) return rc;
-  if ((rc = gemm<false, true>(st, xp + Cin, W1, Hp + 3L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 0)) < 0) return rc;
+  if ((rc = gemm<false, true>(t, st, xp + Cin, W0, Hp + 2L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 0)) < 0) return rc;
+  if ((rc = gemm<false, true>(t, st, xp, W2, Hp + 2L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 1)) < 0) return rc;
+  if ((rc = gemm<false, true>(t, st, xp + Cin, W1, Hp + 3L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 0)) < 0) return rc;
   // layer-norm backward over the 2T output rows of every utterance (output row u of utterance b is flat row 2 b (T + 1) + 2 + u)
   const int nblk = (int)std::min<long>(256, ((long)B * 2 * T + 3) / 4);
   if (reserve(&t->part, (size_t)nblk * 6 * std::max(Cout, 256) * 4)) return DCTTS_ERR_HIP;
@@ -316,14 +329,14 @@ extern "C" int dctts_train_conv1d_transpose_backward(dctts_train* t, const float
   const float* Aw[3] = {dHp + 2L * Cout, dHp + 3L * Cout, dHp + 2L * Cout};
   const float* Bw[3] = {xp + Cin, xp + Cin, xp};
   for (int j = 0; j < 3; ++j) {
-    const int nz = gemm<true, false>(st, Aw[j], Bw[j], (float*)t->wpart.p, Cout, Cin, M, 2 * Cout, Cin, Cin, 0, splits, wsz);
+    const int nz = gemm<true, false>(t, st, Aw[j], Bw[j], (float*)t->wpart.p, Cout, Cin, M, 2 * Cout, Cin, Cin, 0, splits, wsz);
     if (nz < 0) return nz;
     hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((wsz + 255) / 256)), dim3(256), 0, st, (const float*)t->wpart.p, nz, wsz, wsz, dkernel + (long)j * wsz);
     THIP(hipGetLastError());
   }
-  if ((rc = gemm<false, false>(st, dHp + 2L * Cout, W0, dxp + Cin, M, Cin, Cout, 2 * Cout, Cin, Cin, 0)) < 0) return rc;
-  if ((rc = gemm<false, false>(st, dHp + 3L * Cout, W1, dxp + Cin, M, Cin, Cout, 2 * Cout, Cin, Cin, 1)) < 0) return rc;
-  if ((rc = gemm<false, false>(st, dHp + 4L * Cout, W2, dxp + Cin, M, Cin, Cout, 2 * Cout, Cin, Cin, 1)) < 0) return rc;
+  if ((rc = gemm<false, false>(t, st, dHp + 2L * Cout, W0, dxp + Cin, M, Cin, Cout, 2 * Cout, Cin, Cin, 0)) < 0) return rc;
+  if ((rc = gemm<false, false>(t, st, dHp + 3L * Cout, W1, dxp + Cin, M, Cin, Cout, 2 * Cout, Cin, Cin, 1)) < 0) return rc;
+  if ((rc = gemm<false, false>(t, st, dHp + 4L * Cout, W2, dxp + Cin, M, Cin, Cout, 2 * Cout, Cin, Cin, 1)) < 0) return rc;
   const long m4 = (long)B * T * (Cin / 4);
   hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((m4 + 255) / 256)), dim3(256), 0, st, dxp, dx, B, T, T + 1, 1, Cin, 1);
   THIP(hipGetLastError());
@@ -384,9 +397,9 @@ extern "C" int dctts_train_conv1d_transpose_forward(dctts_train* t, const float*
   const long wsz = (long)Cout * Cin;
   const int M = (int)(R - 1);
   int rc;
-  if ((rc = gemm<false, true>(st, xp + Cin, kernel, Hp + 2L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 0)) < 0) return rc;
-  if ((rc = gemm<false, true>(st, xp, kernel + 2 * wsz, Hp + 2L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 1)) < 0) return rc;
-  if ((rc = gemm<false, true>(st, xp + Cin, kernel + wsz, Hp + 3L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 0)) < 0) return rc;
+  if ((rc = gemm<false, true>(t, st, xp + Cin, kernel, Hp + 2L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 0)) < 0) return rc;
+  if ((rc = gemm<false, true>(t, st, xp, kernel + 2 * wsz, Hp + 2L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 1)) < 0) return rc;
+  if ((rc = gemm<false, true>(t, st, xp + Cin, kernel + wsz, Hp + 3L * Cout, M, Cout, Cin, Cin, Cin, 2 * Cout, 0)) < 0) return rc;
   CFwdRowsParams q{B, 2 * T, 2 * (T + 1), Cout, Cout, 2, Hp, bias, gamma, beta, 0, y};
   hipLaunchKernelGGL(c_fwd_rows_kernel, dim3((unsigned)(((long)B * 2 * T + 3) / 4)), dim3(256), 0, st, q);
   THIP(hipGetLastError());
@@ -433,10 +446,10 @@ extern "C" int dctts_train_attention_forward(dctts_train* t, const float* Q, con
   if (reserve(&t->att, (size_t)2 * rows * Np * 4)) return DCTTS_ERR_HIP;
   float* A = (float*)t->att.p;
   int rc;
-  if ((rc = gemm_batched<false, true>(st, B, Q, (long)T * d, K, (long)N * d, A, (long)T * Np, T, N, d, d, d, Np, 0))) return rc;
+  if ((rc = gemm_batched<false, true>(t, st, B, Q, (long)T * d, K, (long)N * d, A, (long)T * Np, T, N, d, d, d, Np, 0))) return rc;
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, A, rows, N, Np, 1.0f / std::sqrt((float)d));
   THIP(hipGetLastError());
-  if ((rc = gemm_batched<false, false>(st, B, A, (long)T * Np, V, (long)N * d, R, (long)T * 2 * d, T, d, N, Np, d, 2 * d, 0))) return rc;
+  if ((rc = gemm_batched<false, false>(t, st, B, A, (long)T * Np, V, (long)N * d, R, (long)T * 2 * d, T, d, N, Np, d, 2 * d, 0))) return rc;
   hipLaunchKernelGGL(scatter_cols_kernel, dim3((unsigned)((rows * d + 255) / 256)), dim3(256), 0, st, Q, R + d, 2 * d, rows, d);
   THIP(hipGetLastError());
   hipLaunchKernelGGL(transpose_kernel, dim3((unsigned)((rows * N + 255) / 256)), dim3(256), 0, st, (const float*)A, alignments, B, T, N, Np);
@@ -459,19 +472,19 @@ extern "C" int dctts_train_attention_backward(dctts_train* t, const float* Q, co
   const float scale = 1.0f / std::sqrt((float)d);
   int rc;
   // A = softmax(Q K^T * scale)
-  if ((rc = gemm_batched<false, true>(st, B, Q, (long)T * d, K, (long)N * d, A, (long)T * Np, T, N, d, d, d, Np, 0))) return rc;
+  if ((rc = gemm_batched<false, true>(t, st, B, Q, (long)T * d, K, (long)N * d, A, (long)T * Np, T, N, d, d, d, Np, 0))) return rc;
   hipLaunchKernelGGL(softmax_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, A, rows, N, Np, scale);
   THIP(hipGetLastError());
   // dA = dR[:, :, :d] V^T (+ dAl^T in the row kernel);  dV = A^T dR[:, :, :d]
-  if ((rc = gemm_batched<false, true>(st, B, dR, (long)T * 2 * d, V, (long)N * d, dA, (long)T * Np, T, N, d, 2 * d, d, Np, 0))) return rc;
-  if ((rc = gemm_batched<true, false>(st, B, A, (long)T * Np, dR, (long)T * 2 * d, dV, (long)N * d, N, d, T, Np, 2 * d, d, 0))) return rc;
+  if ((rc = gemm_batched<false, true>(t, st, B, dR, (long)T * 2 * d, V, (long)N * d, dA, (long)T * Np, T, N, d, 2 * d, d, Np, 0))) return rc;
+  if ((rc = gemm_batched<true, false>(t, st, B, A, (long)T * Np, dR, (long)T * 2 * d, dV, (long)N * d, N, d, T, Np, 2 * d, d, 0))) return rc;
   hipLaunchKernelGGL(softmax_bwd_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, (const float*)A, dA, dAl, B, T, N, Np, scale);
   THIP(hipGetLastError());
   // dQ = dS K + dR[:, :, d:];  dK = dS^T Q      (the 1 / sqrt(d) is folded into dS)
   hipLaunchKernelGGL(copy_cols_kernel, dim3((unsigned)((rows * d + 255) / 256)), dim3(256), 0, st, dR + d, 2 * d, dQ, rows, d);
   THIP(hipGetLastError());
-  if ((rc = gemm_batched<false, false>(st, B, dA, (long)T * Np, K, (long)N * d, dQ, (long)T * d, T, d, N, Np, d, d, 1))) return rc;
-  if ((rc = gemm_batched<true, false>(st, B, dA, (long)T * Np, Q, (long)T * d, dK, (long)N * d, N, d, T, Np, d, d, 0))) return rc;
+  if ((rc = gemm_batched<false, false>(t, st, B, dA, (long)T * Np, K, (long)N * d, dQ, (long)T * d, T, d, N, Np, d, d, 1))) return rc;
+  if ((rc = gemm_batched<true, false>(t, st, B, dA, (long)T * Np, Q, (long)T * d, dK, (long)N * d, N, d, T, Np, d, d, 0))) return rc;
   return 0;
 }
 

@@ -98,7 +98,9 @@ def network_backward(ops: "TrainOps", layers, W: Dict[str, torch.Tensor], prefix
 class TrainOps:
     """Device workspaces + the training-slice entry points for one GPU."""
 
-    def __init__(self, device: int = None):
+    def __init__(self, device: int = None, split_bf16_terms: int = 0):
+        """split_bf16_terms: 0 = every contraction on the fp32 matrix instruction (default), 3 = on the bf16 matrix pipe from three exact
+        bf16 terms per operand element (dctts_train_set_split_bf16_terms; fp32-grade gradients)."""
         if not torch.cuda.is_available():
             raise DcttsError("dc_tts_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         self.lib = _lib.load()
@@ -107,6 +109,13 @@ class TrainOps:
         h = ctypes.c_void_p()
         self._ok(self.lib.dctts_train_create(ctypes.byref(h), self.device_index))
         self._h = h
+        if split_bf16_terms:
+            self.set_split_bf16_terms(split_bf16_terms)
+
+    def set_split_bf16_terms(self, terms: int):
+        """0: fp32 MFMA contractions; 3: three-term split-bf16 contractions (forward passes, both gradients, attention).  Nothing is packed: may
+        change between any two calls.  Any other value raises."""
+        self._ok(self.lib.dctts_train_set_split_bf16_terms(self._h, int(terms)))
 
     def _ok(self, rc: int):
         if rc != 0:
@@ -346,13 +355,13 @@ class TrainGraph:
     reproduced.  The loop around it (train.py:137-162: batches from data_load.get_batch, a checkpoint every 1000 steps, resume from
     the newest one) is `main` below; TensorBoard summaries (train.py:112-113,133) are not written."""
 
-    def __init__(self, num: int, weights, hp, device: int = None, training: bool = True, seed: int = 0):
+    def __init__(self, num: int, weights, hp, device: int = None, training: bool = True, seed: int = 0, split_bf16_terms: int = 0):
         from .layers import audiodec_layers, audioenc_layers, ssrn_layers, textenc_layers
         if num not in (1, 2):
             raise ValueError("num: 1 = Text2Mel, 2 = SSRN (train.py:141)")
         self.num, self.hp = num, hp
         self.training, self.seed = bool(training), int(seed)       # training=True: dropout hp.dropout_rate behind every block (train.py:55-72)
-        self.ops = TrainOps(device)
+        self.ops = TrainOps(device, split_bf16_terms=split_bf16_terms)       # 3: the step's contractions on the bf16 matrix pipe (TrainOps)
         prefix = "Text2Mel/" if num == 1 else "SSRN/"
         import numpy as _np
         self.W = {n: torch.from_numpy(_np.ascontiguousarray(v, dtype=_np.float32)).to(self.ops.device) for n, v in weights.items() if n.startswith(prefix)}
@@ -479,6 +488,8 @@ def main(argv=None, hp=None, save_every: int = 1000, batches=None, init_seed: in
     ap.add_argument("--prepro-dir", default=".", help="directory holding mels/ and mags/ written by `python -m dc_tts_amd.prepo`")
     ap.add_argument("--logdir", default=None, help="hp.logdir; '-<num>' is appended")
     ap.add_argument("--num-iterations", type=int, default=None)
+    ap.add_argument("--split-bf16-terms", type=int, choices=(0, 3), default=0,
+                    help="0: fp32 matrix instructions (default); 3: every contraction of the step from three exact bf16 terms on the bf16 matrix pipe")
     args = ap.parse_args(argv)
     if args.data: hp = hp.replace(data=args.data)
     if args.logdir: hp = hp.replace(logdir=args.logdir)
@@ -486,7 +497,7 @@ def main(argv=None, hp=None, save_every: int = 1000, batches=None, init_seed: in
     num = args.num
     # the reference's initialisers (modules.py / tf.layers defaults): variance-scaling truncated-normal kernels, truncated normal 0.1 for the
     # embedding, layer-norm gamma = 1, beta = 0, conv bias = 0 -- perturb=False; the perturbed variant is for parity tests only
-    g = TrainGraph(num, initial_variables(hp, init_seed), hp)
+    g = TrainGraph(num, initial_variables(hp, init_seed), hp, **({"split_bf16_terms": args.split_bf16_terms} if args.split_bf16_terms else {}))
     logdir = hp.logdir + "-" + str(num)
     resumed = g.restore(logdir)
     print("Training Graph loaded" + (" (resumed at global_step %d)" % g.global_step if resumed else ""), file=sys.stderr)

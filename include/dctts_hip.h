@@ -156,6 +156,18 @@ int dctts_set_split_bf16(dctts_ctx* ctx, int mode);
  * DCTTS_ERR_ARG.  Measured error and time: tests/test_gpu_split_bf16_terms.py, DESIGN.md section 11. */
 int dctts_set_split_bf16_terms(dctts_ctx* ctx, int terms);
 
+/* The same choice for the TRAINING path (handle of dctts_train.h): which arithmetic its contractions run: every GEMM behind the hc / conv1d / conv1d_transpose forward and backward passes (pre-norm
+ * tensors, input gradients, split-K weight gradients) and the attention forward and backward.  terms = 0 (default): v_mfma_f32_32x32x2_f32, exact fp32 products.
+ * terms = 3: every element of BOTH operands is written as hi + mid + lo, three bf16 terms that carry all 24 mantissa bits (x = hi + mid + lo exactly), inside the
+ * GEMM on its way into LDS, and a product is accumulated in fp32 from SIX v_mfma_f32_32x32x16_bf16 instructions, small products first: lo.hi + hi.lo + mid.mid +
+ * mid.hi + hi.mid + hi.hi.  What is dropped (mid.lo + lo.mid + lo.lo) is <= ~2^-26 of |a||b| per product, below one fp32 accumulate rounding: fp32-grade
+ * gradients on the bf16 matrix pipe.  The row kernels (layer-norm, gate, softmax, losses, dropout, Adam) are fp32 either way.  Nothing is packed, so the setting may
+ * change between any two calls and the tape is unaffected; sums keep their fixed order (bitwise reproducible in either form).  Two differences from the fp32 form: an
+ * infinite operand gives NaN (inf - inf in the split) where fp32 gives +-inf, and operands below ~2^-100 lose their low terms to bf16 underflow.  Anything but 0 or 3
+ * is DCTTS_ERR_ARG.  Measured error and time: tests/test_gpu_train_split_bf16.py, DESIGN.md section 10, profiles/train_split_bf16.txt. */
+struct dctts_train;
+int dctts_train_set_split_bf16_terms(struct dctts_train* t, int terms);
+
 /* Workspaces and the decode's device tables are cached per geometry (B, T, N) and only grow: a serving loop that alternates
  * between batch shapes pays an allocation the first time a shape is seen and nothing afterwards (no hipDeviceSynchronize, no
  * hipFree on a shape change).  When the cached workspaces exceed `bytes` (default 96 GiB of the 288 GB) the next call drops

@@ -41,6 +41,9 @@ size_t dctts_train_device_bytes(const dctts_train* t);
  * silently recomputes.  Every call (enable 0 or 1) empties the tape: call it at the start of each training step. */
 int dctts_train_tape(dctts_train* t, int enable);
 
+/* Which arithmetic the contractions behind these calls run (fp32 matrix instructions by default, or three exact bf16 terms per operand element on the bf16
+ * matrix pipe) is a switch of the handle: dctts_train_set_split_bf16_terms, declared in dctts_hip.h beside the inference path's dctts_set_split_bf16_terms. */
+
 /* Backward of y = hc(x) (modules.py:143-197: conv1d(k, dilation `rate`, SAME or CAUSAL padding) to 2C channels -> split ->
  * layer-norm(H1), layer-norm(H2) -> sigmoid(H1) * H2 + (1 - sigmoid(H1)) * x, training=False dropout i.e. none).
  *   x, dy, dx            (B, T, C)          C a multiple of 256, k in {1, 3}
