@@ -67,6 +67,8 @@ SYMBOLS = {
     "dctts_vocoder_device_bytes": (c_size_t, [c_void_p]),
     "dctts_spectrogram2wav": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dctts_griffin_lim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dctts_vocoder_set_mel_basis": (c_int, [c_void_p, c_void_p, c_int]),
+    "dctts_wav2spectrograms": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dctts_vocoder_prof_enable": (c_int, [c_void_p, c_int]),
     "dctts_vocoder_prof_collect": (c_int, [c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(ctypes.c_double)]),
     # include/dctts_train.h (first training slice)

@@ -20,19 +20,22 @@ constexpr int FW_EX = FW_N + FW_N / 16 + 2;       // padded exchange buffer (flo
 
 FW_HD int fw_idx(int i) { return i + (i >> 4); }   // one pad slot per 16: lane-strided 16-float2 rows stop sharing banks
 
-FW_HD float2 fw_mul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-FW_HD float2 fw_mulc(float2 a, float2 b) { return make_float2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a * conj(b)
+// make_float2 without the call: the HIP header's is a plain inline function, which a kernel compiled with target features of its own (analysis_kernels.h)
+// cannot inline
+FW_HD float2 fw_f2(float x, float y) { float2 r; r.x = x; r.y = y; return r; }
+FW_HD float2 fw_mul(float2 a, float2 b) { return fw_f2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+FW_HD float2 fw_mulc(float2 a, float2 b) { return fw_f2(a.x * b.x + a.y * b.y, a.y * b.x - a.x * b.y); }   // a * conj(b)
 template <bool INV> FW_HD float2 fw_tw(float2 a, float2 w) { return INV ? fw_mulc(a, w) : fw_mul(a, w); }      // w = e^{-i..}
 
 // 4-point DFT in place: (a,b,c,d) <- (y0,y1,y2,y3), y_r = sum_q x_q (-/+ i)^{q r}
 template <bool INV> FW_HD void fw_dft4(float2& a, float2& b, float2& c, float2& d) {
-  const float2 s0 = make_float2(a.x + c.x, a.y + c.y), d0 = make_float2(a.x - c.x, a.y - c.y);
-  const float2 s1 = make_float2(b.x + d.x, b.y + d.y), d1 = make_float2(b.x - d.x, b.y - d.y);
-  const float2 r = INV ? make_float2(-d1.y, d1.x) : make_float2(d1.y, -d1.x);     // (b-d) * (+i | -i)
-  a = make_float2(s0.x + s1.x, s0.y + s1.y);
-  b = make_float2(d0.x + r.x, d0.y + r.y);
-  c = make_float2(s0.x - s1.x, s0.y - s1.y);
-  d = make_float2(d0.x - r.x, d0.y - r.y);
+  const float2 s0 = fw_f2(a.x + c.x, a.y + c.y), d0 = fw_f2(a.x - c.x, a.y - c.y);
+  const float2 s1 = fw_f2(b.x + d.x, b.y + d.y), d1 = fw_f2(b.x - d.x, b.y - d.y);
+  const float2 r = INV ? fw_f2(-d1.y, d1.x) : fw_f2(d1.y, -d1.x);     // (b-d) * (+i | -i)
+  a = fw_f2(s0.x + s1.x, s0.y + s1.y);
+  b = fw_f2(d0.x + r.x, d0.y + r.y);
+  c = fw_f2(s0.x - s1.x, s0.y - s1.y);
+  d = fw_f2(d0.x - r.x, d0.y - r.y);
 }
 
 // v * W_16^m (forward) or its conjugate (inverse); m is a compile-time constant at every call site after unrolling
@@ -49,7 +52,7 @@ template <bool INV> FW_HD float2 fw_w16(float2 v, int m) {
     default: c = -C1; s = -S1; break;     // m == 9
   }
   if (INV) s = -s;
-  return make_float2(v.x * c + v.y * s, v.y * c - v.x * s);
+  return fw_f2(v.x * c + v.y * s, v.y * c - v.x * s);
 }
 
 // 16-point DFT, natural order in and out:  n = n1 + 4 n2,  k = 4 k1 + k2

@@ -1,5 +1,6 @@
 // vocoder_api.hip -- host side of the vocoder tail (include/dctts_hip.h: dctts_vocoder_*, dctts_spectrogram2wav,
-// dctts_griffin_lim).  Replaces utils.py:67-114 as called per utterance from synthesize.py:61-64.
+// dctts_griffin_lim).  Replaces utils.py:67-114 as called per utterance from synthesize.py:61-64.  The same handle runs the
+// analysis direction (dctts_wav2spectrograms: utils.py:18-65 + the frame reduction of :155-164, analysis_kernels.h).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -14,6 +15,7 @@
 #include "../../include/dctts_hip.h"
 #include "api_common.h"
 #include "vocoder_kernels.h"
+#include "analysis_kernels.h"
 
 using namespace dctts;
 
@@ -35,7 +37,8 @@ struct dctts_vocoder {
   float2 *w1024 = nullptr, *w2048 = nullptr;
   int wss_frames = 0;
   int wave_kernel = 1;     // register budget of the iteration kernel: 1 = 3 waves/SIMD without spills, 2 = 4 waves/SIMD (DCTTS_VOC_WAVE)
-  VBuf spec, X, fr0, fr1, yraw, pw;
+  VBuf spec, X, fr0, fr1, yraw, pw, aws;
+  int4* bands = nullptr; float* bandw = nullptr; int n_mels = 0;      // dctts_vocoder_set_mel_basis: band table + compact weights
   bool prof = false;                                  // HIP events around every gl_iter_wave launch (dctts_vocoder_prof_*)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
   // One set of scratch buffers per handle: calls from different streams are ordered on the device (a call waits for the completion event of the last call that
@@ -107,7 +110,9 @@ extern "C" int dctts_vocoder_destroy(dctts_vocoder* v) {
   (void)hipSetDevice(v->device);
   (void)hipDeviceSynchronize();
   for (auto& e : v->prof_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  for (VBuf* b : {&v->spec, &v->X, &v->fr0, &v->fr1, &v->yraw, &v->pw}) if (b->p) (void)hipFree(b->p);
+  for (VBuf* b : {&v->spec, &v->X, &v->fr0, &v->fr1, &v->yraw, &v->pw, &v->aws}) if (b->p) (void)hipFree(b->p);
+  if (v->bands) (void)hipFree(v->bands);
+  if (v->bandw) (void)hipFree(v->bandw);
   if (v->done) (void)hipEventDestroy(v->done);
   if (v->window) (void)hipFree(v->window);
   if (v->wss) (void)hipFree(v->wss);
@@ -225,6 +230,85 @@ extern "C" int dctts_spectrogram2wav(dctts_vocoder* v, const float* mag, int B, 
   return guard.release();
 }
 
+// The mel basis is banded (each filter is one triangle): row m becomes (lo, width, offset) + its width non-zero weights, which is what the
+// kernel's 16-lane gather walks.
+extern "C" int dctts_vocoder_set_mel_basis(dctts_vocoder* v, const float* basis_host, int n_mels) {
+  if (!v || !basis_host) return dctts_set_error(DCTTS_ERR_ARG, "null argument");
+  if (n_mels < 4 || n_mels % 4 != 0) return dctts_set_error(DCTTS_ERR_ARG, "n_mels must be a positive multiple of 4 (four bands per wave round)");
+  std::vector<int4> bands((size_t)n_mels);
+  std::vector<float> w;
+  for (int m = 0; m < n_mels; ++m) {
+    const float* row = basis_host + (size_t)m * VOC_BINS;
+    int lo = VOC_BINS, hi = -1;
+    for (int k = 0; k < VOC_BINS; ++k) if (row[k] != 0.f) { if (k < lo) lo = k; hi = k; }
+    const int width = hi < 0 ? 0 : hi - lo + 1;
+    if (hi < 0) lo = 0;
+    for (int k = lo; k < lo + width; ++k)
+      if (row[k] == 0.f) return dctts_set_error(DCTTS_ERR_ARG, "mel basis row " + std::to_string(m) + ": the non-zeros are not one contiguous run");
+    if (width > AN_BAND_MAX)
+      return dctts_set_error(DCTTS_ERR_ARG, "mel basis row " + std::to_string(m) + ": band of " + std::to_string(width) + " bins > " + std::to_string(AN_BAND_MAX));
+    bands[m] = make_int4(lo, width, (int)w.size(), 0);
+    w.insert(w.end(), row + lo, row + lo + width);
+  }
+  for (auto& bd : bands) bd.w = (int)w.size();            // lanes past a band's width read this zero weight instead of branching
+  w.push_back(0.f);
+  VHIPCHK(hipSetDevice(v->device));
+  std::lock_guard<std::mutex> lk(v->mu);
+  VHIPCHK(hipDeviceSynchronize());                        // a call in flight may be reading the previous tables
+  if (v->bands) { VHIPCHK(hipFree(v->bands)); v->bands = nullptr; }
+  if (v->bandw) { VHIPCHK(hipFree(v->bandw)); v->bandw = nullptr; }
+  v->n_mels = 0;
+  VHIPCHK(hipMalloc((void**)&v->bands, bands.size() * sizeof(int4)));
+  VHIPCHK(hipMalloc((void**)&v->bandw, w.size() * sizeof(float)));
+  VHIPCHK(hipMemcpy(v->bands, bands.data(), bands.size() * sizeof(int4), hipMemcpyHostToDevice));
+  VHIPCHK(hipMemcpy(v->bandw, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
+  v->n_mels = n_mels;
+  return 0;
+}
+
+extern "C" int dctts_wav2spectrograms(dctts_vocoder* v, const float* wav, const int32_t* lengths, int B, int Lmax, int trim, int r,
+                                      float* mel, float* mag, int32_t* n_frames, int32_t* bounds, void* stream) {
+  if (!v || !wav || !lengths) return dctts_set_error(DCTTS_ERR_ARG, "null argument");
+  if (B < 1 || r < 1) return dctts_set_error(DCTTS_ERR_ARG, "B and r must be positive");
+  if (Lmax <= VOC_NFFT / 2) return dctts_set_error(DCTTS_ERR_ARG, "Lmax must exceed n_fft/2 (reflect padding)");
+  if (Lmax > 0x3fffffff) return dctts_set_error(DCTTS_ERR_ARG, "utterance too long");
+  const int hop = v->cfg.hop_length;
+  const int Fmax = 1 + Lmax / hop, Fpad = (Fmax + r - 1) / r * r;
+  if ((long)B * Fpad > 0x0fffffffL) return dctts_set_error(DCTTS_ERR_ARG, "too many frames for one call");
+  VHIPCHK(hipSetDevice(v->device));
+  std::lock_guard<std::mutex> lk(v->mu);
+  if (mel && !v->bands) return dctts_set_error(DCTTS_ERR_STATE, "dctts_vocoder_set_mel_basis has not been called");
+  hipStream_t st = (hipStream_t)stream;
+  VocGuard guard(v, st);
+  VCHK(guard.acquire());
+  VCHK(vgrow(v->aws, (size_t)B * 3 * sizeof(int)));
+  int* ws = (int*)v->aws.p;
+  if (trim) {
+    const int flen = v->cfg.trim_frame_length, fhop = v->cfg.trim_hop_length;
+    const int n_tf = 1 + Lmax / fhop;
+    VCHK(vgrow(v->pw, (size_t)B * n_tf * sizeof(float)));
+    hipLaunchKernelGGL(frame_power_ragged_kernel, dim3(n_tf, B), dim3(256), 0, st, wav, (const int*)lengths, (float*)v->pw.p, Lmax, n_tf, flen, fhop);
+    hipLaunchKernelGGL(trim_bounds_ragged_kernel, dim3(B), dim3(256), 0, st, (const float*)v->pw.p, (const int*)lengths, Lmax, n_tf, flen, fhop,
+                       v->cfg.trim_top_db, hop, ws, (int*)bounds, (int*)n_frames);
+  } else {
+    hipLaunchKernelGGL(full_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, st, (const int*)lengths, B, Lmax, hop, ws, (int*)bounds, (int*)n_frames);
+  }
+  if (mel || mag) {
+    AnGeom g;
+    g.Lmax = Lmax; g.Fpad = Fpad; g.r = r; g.n_mels = v->n_mels;
+    g.hop = hop;
+    g.preemph = v->cfg.preemphasis; g.max_db = v->cfg.max_db; g.ref_db = v->cfg.ref_db;
+    g.window = v->window; g.w1024 = v->w1024; g.w2048 = v->w2048; g.bands = v->bands; g.bandw = v->bandw;
+    const int n_items = B * Fpad, per_xcd = (n_items + 7) / 8;
+    if ((v->lpad >> 7) >= 3 && ((v->lpad + v->cfg.win_length - 1) >> 7) <= 12)      // the window's first and last lane-strided slot
+      hipLaunchKernelGGL((analysis_wave_kernel<3, 12>), dim3(8 * per_xcd), dim3(64), 0, st, g, wav, (const int*)ws, mag, mel, n_items, per_xcd);
+    else
+      hipLaunchKernelGGL((analysis_wave_kernel<0, 15>), dim3(8 * per_xcd), dim3(64), 0, st, g, wav, (const int*)ws, mag, mel, n_items, per_xcd);
+  }
+  VHIPCHK(hipGetLastError());
+  return guard.release();
+}
+
 extern "C" int dctts_vocoder_prof_enable(dctts_vocoder* v, int enable) {
   if (!v) return dctts_set_error(DCTTS_ERR_ARG, "null handle");
   v->prof = enable != 0;
@@ -248,5 +332,5 @@ extern "C" int dctts_vocoder_prof_collect(dctts_vocoder* v, int* launches, doubl
 
 extern "C" size_t dctts_vocoder_device_bytes(const dctts_vocoder* v) {
   if (!v) return 0;
-  return v->spec.bytes + v->X.bytes + v->fr0.bytes + v->fr1.bytes + v->yraw.bytes + v->pw.bytes;
+  return v->spec.bytes + v->X.bytes + v->fr0.bytes + v->fr1.bytes + v->yraw.bytes + v->pw.bytes + v->aws.bytes;
 }

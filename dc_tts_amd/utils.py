@@ -6,8 +6,12 @@ Same names and argument meaning as the reference, with two differences that the 
     batch (B, T, 1 + n_fft//2); the reference's internal transpose to librosa's (1 + n_fft//2, T) never happens;
   * batched calls return a list of trimmed float32 waveforms (utterances trim to different lengths).
 All arithmetic runs in libdctts_hip.so (csrc/vocoder_kernels.h); there is no CPU fallback.
+
+The analysis direction, `get_spectrograms` (utils.py:18-65) and `load_spectrograms` (utils.py:147-165), is here too (csrc/analysis_kernels.h): one path as
+in the reference, or a list of paths served by one batched call.  `dc_tts_amd.audio` keeps the host numpy form, which stays the default of prepo / get_batch.
 """
 import ctypes
+import os
 from typing import List, Optional, Tuple
 
 import numpy as np
@@ -93,6 +97,38 @@ class Vocoder:
         self._ok(self.lib.dctts_griffin_lim(self._h, _ptr(spec), B, F, n_iter, _ptr(y), _ptr(X), self._stream()))
         return (y, torch.view_as_complex(X)) if want_X else y
 
+    def set_mel_basis(self, basis: np.ndarray):
+        """basis (n_mels, 1 + n_fft//2), what librosa.filters.mel returns: packed into the kernel's band table (banded rows only)."""
+        basis = np.ascontiguousarray(basis, dtype=np.float32)
+        if basis.ndim != 2 or basis.shape[1] != self.hp.n_linear:
+            raise ValueError(f"basis: expected (n_mels, {self.hp.n_linear}), got {basis.shape}")
+        self._ok(self.lib.dctts_vocoder_set_mel_basis(self._h, basis.ctypes.data_as(ctypes.c_void_p), basis.shape[0]))
+        self._n_mels = basis.shape[0]
+
+    def wav2spectrograms_device(self, wav: torch.Tensor, lengths: torch.Tensor, r: int = 1, trim: bool = True):
+        """utils.py:18-65 for a ragged batch, nothing leaves the GPU: wav (B, Lmax) float32 zero-filled past each length, lengths (B) int32 ->
+        mel (B, Fpad/r, n_mels) [frames 0, r, 2r, ...], mag (B, Fpad, 1+n_fft//2), n_frames (B) int32, bounds (B, 2) int32 [the trimmed range], with
+        Fpad = 1 + Lmax//hop rounded up to a multiple of r.  Rows at or past n_frames[b] are zero (load_spectrograms' padding); n_frames 0 = nothing but
+        zeros in the clip, -1 = too short to reflect-pad (at most n_fft//2 samples before or after the trim)."""
+        _check(wav, "wav", torch.float32, 2, self.device)
+        _check(lengths, "lengths", torch.int32, 1, self.device)
+        B, Lmax = wav.shape
+        if lengths.shape[0] != B:
+            raise ValueError(f"lengths: {lengths.shape[0]} entries for {B} utterances")
+        if r < 1:
+            raise ValueError("r must be >= 1")
+        if getattr(self, "_n_mels", None) is None:
+            from .audio import mel_filterbank
+            self.set_mel_basis(mel_filterbank(self.hp.sr, self.hp.n_fft, self.hp.n_mels))
+        Fpad = -(-(1 + Lmax // self.hp.hop_length) // r) * r
+        mel = torch.empty(B, Fpad // r, self._n_mels, dtype=torch.float32, device=self.device)
+        mag = torch.empty(B, Fpad, self.hp.n_linear, dtype=torch.float32, device=self.device)
+        n_frames = torch.empty(B, dtype=torch.int32, device=self.device)
+        bounds = torch.empty(B, 2, dtype=torch.int32, device=self.device)
+        self._ok(self.lib.dctts_wav2spectrograms(self._h, _ptr(wav), _ptr(lengths), B, Lmax, int(bool(trim)), int(r), _ptr(mel), _ptr(mag),
+                                                 _ptr(n_frames), _ptr(bounds), self._stream()))
+        return mel, mag, n_frames, bounds
+
 
 _default: dict = {}
 
@@ -120,6 +156,46 @@ def spectrogram2wav(mag, hp: Hyperparams = _hp, vocoder: Optional[Vocoder] = Non
     wav, bounds = v.spectrogram2wav_device(m)
     wav_h, b_h = wav.cpu().numpy(), bounds.cpu().numpy()
     out: List[np.ndarray] = [wav_h[i, b_h[i, 0]:b_h[i, 1]].copy() for i in range(wav_h.shape[0])]
+    return out[0] if single else out
+
+
+def _spectrograms(fpath_or_list, hp: Hyperparams, r: int, vocoder: Optional[Vocoder]):
+    """The files' waveforms, padded to the longest, through ONE wav2spectrograms_device call -> per file (fname, mel rows, mag rows, n_frames)."""
+    from .audio import load_wav
+    single = isinstance(fpath_or_list, (str, os.PathLike))
+    fpaths = [fpath_or_list] if single else list(fpath_or_list)
+    v = vocoder or _vocoder(hp, None)
+    ys = [load_wav(f, hp.sr) for f in fpaths]
+    Lmax = max([len(y) for y in ys] + [hp.n_fft // 2 + 1])             # (a batch of too-short clips is reported per file below, not by the call)
+    wav = torch.zeros(len(ys), Lmax, dtype=torch.float32).pin_memory()
+    for i, y in enumerate(ys):
+        wav[i, :len(y)] = torch.from_numpy(y)
+    lengths = torch.tensor([len(y) for y in ys], dtype=torch.int32)
+    mel, mag, n_frames, _ = v.wav2spectrograms_device(wav.to(v.device, non_blocking=True), lengths.to(v.device), r=r, trim=True)
+    mel, mag, n_frames = mel.cpu().numpy(), mag.cpu().numpy(), n_frames.cpu().numpy()
+    out = []
+    for i, f in enumerate(fpaths):
+        nf = int(n_frames[i])
+        if nf <= 0:
+            raise ValueError(f"get_spectrograms: {f}: " + ("nothing left after trimming (silent file)" if nf == 0 else
+                                                            f"at most n_fft/2 = {hp.n_fft // 2} samples (before or after trimming)"))
+        rows = -(-nf // r)
+        out.append((os.path.basename(f), mel[i, :rows].copy(), mag[i, :rows * r].copy()))
+    return out, single
+
+
+def get_spectrograms(fpath_or_list, hp: Hyperparams = _hp, vocoder: Optional[Vocoder] = None):
+    """utils.py:18-65 on the GPU: one path -> (mel (T, n_mels), mag (T, 1+n_fft//2)) float32 as `audio.get_spectrograms`; a list of paths ->
+    a list of such pairs from one batched call.  WAV decoding stays on the host."""
+    out, single = _spectrograms(fpath_or_list, hp, 1, vocoder)
+    out = [(mel, mag) for _, mel, mag in out]
+    return out[0] if single else out
+
+
+def load_spectrograms(fpath_or_list, hp: Hyperparams = _hp, vocoder: Optional[Vocoder] = None):
+    """utils.py:147-165 on the GPU: (fname, mel (T/r, n_mels), mag (T, 1+n_fft//2)) with T padded to a multiple of hp.r, as `audio.load_spectrograms`;
+    a list of paths -> a list of such triples from one batched call."""
+    out, single = _spectrograms(fpath_or_list, hp, hp.r, vocoder)
     return out[0] if single else out
 
 

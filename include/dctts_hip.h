@@ -214,6 +214,25 @@ int dctts_spectrogram2wav(dctts_vocoder* v, const float* mag, int B, int F, floa
  * iteration produced (needs n_iter >= 1).  n_iter = 0 gives y = istft(spec). */
 int dctts_griffin_lim(dctts_vocoder* v, const float* spec, int B, int F, int n_iter, float* y, float* X_best, void* stream);
 
+/* The analysis direction: utils.py:18-65 get_spectrograms and the frame reduction of load_spectrograms (:155-164) for a RAGGED batch of waveforms.
+ * dctts_vocoder_set_mel_basis: basis_host (n_mels, 1 + n_fft/2) row-major on the HOST, what librosa.filters.mel returns; packed once into a band table
+ * (first bin, width) + the non-zero weights and uploaded.  DCTTS_ERR_ARG if a row's non-zeros are not one contiguous run, a band is wider than 96 bins
+ * (the kernel sums a band with 16 lanes in at most 6 rounds) or n_mels is not a multiple of 4.  The call waits for the device (set-up, not per batch).
+ *
+ * dctts_wav2spectrograms: wav (B, Lmax) float32, zero past each length; lengths (B) int32; both on the DEVICE, as are all outputs.  trim != 0:
+ * librosa.effects.trim per utterance (cfg.trim_*), then y'[n] = y[n] - preemphasis y[n-1], |stft|, mel projection, 20 log10(max(1e-5, .)), normalisation to
+ * [1e-8, 1].  With Fmax = 1 + Lmax / hop_length and Fpad = Fmax rounded up to a multiple of r (>= 1):
+ *   mag (B, Fpad, 1 + n_fft/2) or NULL;   mel (B, Fpad / r, n_mels) or NULL: frames 0, r, 2r, ... (needs the basis: DCTTS_ERR_STATE without it);
+ *   bounds (B, 2) or NULL: the trimmed [start, end) (trim = 0: (0, length));
+ *   n_frames (B) or NULL: F_b = 1 + (end - start) / hop_length, the frames before padding -- rows at or past it are 0.0, which is load_spectrograms' zero
+ *   padding; 0 = nothing left (a clip of zeros; the numpy path keeps such a clip whole and returns floor values); -1 = the untrimmed or the trimmed signal
+ *   has at most n_fft/2 samples, where reflect padding is undefined (all its rows are 0.0).  Neither touches the other utterances.
+ * Stream-ordered, no host synchronisation (workspaces grow with the largest call); results are bitwise reproducible and do not depend on the rest of the
+ * batch.  Lmax must exceed n_fft/2.  The trim decision is taken in fp32, the transform too (audio.py: float64). */
+int dctts_vocoder_set_mel_basis(dctts_vocoder* v, const float* basis_host, int n_mels);
+int dctts_wav2spectrograms(dctts_vocoder* v, const float* wav, const int32_t* lengths, int B, int Lmax, int trim, int r,
+                           float* mel, float* mag, int32_t* n_frames, int32_t* bounds, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
