@@ -67,6 +67,7 @@ SYMBOLS = {
     "dctts_vocoder_device_bytes": (c_size_t, [c_void_p]),
     "dctts_spectrogram2wav": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dctts_griffin_lim": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dctts_vocoder_set_momentum": (c_int, [c_void_p, ctypes.c_float]),
     "dctts_vocoder_set_mel_basis": (c_int, [c_void_p, c_void_p, c_int]),
     "dctts_wav2spectrograms": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dctts_vocoder_prof_enable": (c_int, [c_void_p, c_int]),

@@ -38,6 +38,8 @@ struct dctts_vocoder {
   int wss_frames = 0;
   int wave_kernel = 1;     // register budget of the iteration kernel: 1 = 3 waves/SIMD without spills, 2 = 4 waves/SIMD (DCTTS_VOC_WAVE)
   VBuf spec, X, fr0, fr1, yraw, pw, aws;
+  float momentum = 0.f;    // fast Griffin-Lim (dctts_vocoder_set_momentum); 0 = the reference's loop
+  VBuf ymom;               // its state: the signal of the pass before the last, (B, L); allocated by the first momentum call only
   int4* bands = nullptr; float* bandw = nullptr; int n_mels = 0;      // dctts_vocoder_set_mel_basis: band table + compact weights
   bool prof = false;                                  // HIP events around every gl_iter_wave launch (dctts_vocoder_prof_*)
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_ev;
@@ -110,7 +112,7 @@ extern "C" int dctts_vocoder_destroy(dctts_vocoder* v) {
   (void)hipSetDevice(v->device);
   (void)hipDeviceSynchronize();
   for (auto& e : v->prof_ev) { (void)hipEventDestroy(e.first); (void)hipEventDestroy(e.second); }
-  for (VBuf* b : {&v->spec, &v->X, &v->fr0, &v->fr1, &v->yraw, &v->pw, &v->aws}) if (b->p) (void)hipFree(b->p);
+  for (VBuf* b : {&v->spec, &v->X, &v->fr0, &v->fr1, &v->yraw, &v->pw, &v->aws, &v->ymom}) if (b->p) (void)hipFree(b->p);
   if (v->bands) (void)hipFree(v->bands);
   if (v->bandw) (void)hipFree(v->bandw);
   if (v->done) (void)hipEventDestroy(v->done);
@@ -158,15 +160,25 @@ static int geom(dctts_vocoder* v, int B, int F, VocGeom* g) {
 }
 
 // utils.py:96-106 on device buffers.  spec (B,F,1025) magnitudes -> y (B, L).
+// With momentum (vocoder_kernels.h, gl_iter_wave_body<MOM>) iteration `it` analyses y_it - beta * y_{it-1}, so two signal buffers alternate: pass j
+// (0 = the zero-phase istft, it + 1 = the overlap-add of iteration it) writes the caller's y when n_iter - j is even and ymom otherwise.  The last pass
+// lands in y, the overlap-add of iteration it overwrites y_{it-1} after the iteration kernel has read it (stream order), and both buffers are written
+// in full (passes 0 and 1) before iteration 1 first reads them: nothing of an earlier call is ever read.  Iteration 0 has c_prev = 0: the plain kernel.
 static int run_griffin_lim(dctts_vocoder* v, const VocGeom& g, const float* spec, int B, int n_iter, float2* X_best,
                            float* y, hipStream_t st) {
   VCHK(vgrow(v->fr0, (size_t)B * g.F * g.frs * sizeof(float)));
   float* fr = (float*)v->fr0.p;
+  const bool mom = v->momentum > 0.f && n_iter >= 2;
+  if (mom) VCHK(vgrow(v->ymom, (size_t)B * g.L * sizeof(float)));
+  const float beta = (float)((double)v->momentum / (1.0 + (double)v->momentum));
+  auto ybuf = [&](int j) -> float* { return mom && ((n_iter - j) & 1) ? (float*)v->ymom.p : y; };
   const dim3 grid(g.F, B), ogrid((g.L + 255) / 256, B);
   const int n_items = B * g.F, per_xcd = (n_items + 7) / 8;
   hipLaunchKernelGGL(istft_frames_kernel, grid, dim3(VOC_THREADS), 0, st, g, (const float2*)nullptr, spec, fr);
-  hipLaunchKernelGGL(ola_kernel, ogrid, dim3(256), 0, st, g, (const float*)fr, y);
+  hipLaunchKernelGGL(ola_kernel, ogrid, dim3(256), 0, st, g, (const float*)fr, ybuf(0));
   for (int it = 0; it < n_iter; ++it) {
+    const float* ycur = ybuf(it);
+    float* ynext = ybuf(it + 1);           // with momentum also y_{it-1}, which this iteration reads before its overlap-add replaces it
     if (X_best && it == n_iter - 1) {      // the caller wants the last X_best: un-fused pair for this iteration
       hipLaunchKernelGGL(stft_phase_kernel, grid, dim3(VOC_THREADS), 0, st, g, (const float*)fr, spec, X_best);
       VCHK(vgrow(v->fr1, (size_t)B * g.F * g.frs * sizeof(float)));
@@ -176,12 +188,14 @@ static int run_griffin_lim(dctts_vocoder* v, const VocGeom& g, const float* spec
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (v->prof) { VHIPCHK(hipEventCreate(&e0)); VHIPCHK(hipEventCreate(&e1)); VHIPCHK(hipEventRecord(e0, st)); }
-    if (v->wave_kernel == 2)
-      hipLaunchKernelGGL(gl_iter_wave4_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, (const float*)y, spec, fr, n_items, per_xcd);
+    if (mom && it > 0)                     // (one register budget only: the 4-waves build of this form measured slower and spills)
+      hipLaunchKernelGGL(gl_iter_wave_mom_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, ycur, (const float*)ynext, beta, spec, fr, n_items, per_xcd);
+    else if (v->wave_kernel == 2)
+      hipLaunchKernelGGL(gl_iter_wave4_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, ycur, spec, fr, n_items, per_xcd);
     else
-      hipLaunchKernelGGL(gl_iter_wave_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, (const float*)y, spec, fr, n_items, per_xcd);
+      hipLaunchKernelGGL(gl_iter_wave_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, ycur, spec, fr, n_items, per_xcd);
     if (v->prof) { VHIPCHK(hipEventRecord(e1, st)); v->prof_ev.emplace_back(e0, e1); }
-    hipLaunchKernelGGL(ola_kernel, ogrid, dim3(256), 0, st, g, (const float*)fr, y);
+    hipLaunchKernelGGL(ola_kernel, ogrid, dim3(256), 0, st, g, (const float*)fr, ynext);
   }
   VHIPCHK(hipGetLastError());
   return 0;
@@ -193,6 +207,8 @@ extern "C" int dctts_griffin_lim(dctts_vocoder* v, const float* spec, int B, int
   if (X_best && n_iter == 0) return dctts_set_error(DCTTS_ERR_ARG, "X_best needs n_iter >= 1");
   VHIPCHK(hipSetDevice(v->device));
   std::lock_guard<std::mutex> lk(v->mu);
+  if (X_best && v->momentum > 0.f)
+    return dctts_set_error(DCTTS_ERR_ARG, "X_best comes from the un-fused debug pair, which has no momentum form: set the momentum to 0 for it");
   hipStream_t st = (hipStream_t)stream;
   VocGuard guard(v, st);
   VCHK(guard.acquire());
@@ -228,6 +244,14 @@ extern "C" int dctts_spectrogram2wav(dctts_vocoder* v, const float* mag, int B, 
   }
   VHIPCHK(hipGetLastError());
   return guard.release();
+}
+
+extern "C" int dctts_vocoder_set_momentum(dctts_vocoder* v, float momentum) {
+  if (!v) return dctts_set_error(DCTTS_ERR_ARG, "null handle");
+  if (!(momentum >= 0.f && momentum < 1.f)) return dctts_set_error(DCTTS_ERR_ARG, "momentum must be in [0, 1)");      // (NaN fails both comparisons)
+  std::lock_guard<std::mutex> lk(v->mu);
+  v->momentum = momentum;
+  return 0;
 }
 
 // The mel basis is banded (each filter is one triangle): row m becomes (lo, width, offset) + its width non-zero weights, which is what the
@@ -332,5 +356,5 @@ extern "C" int dctts_vocoder_prof_collect(dctts_vocoder* v, int* launches, doubl
 
 extern "C" size_t dctts_vocoder_device_bytes(const dctts_vocoder* v) {
   if (!v) return 0;
-  return v->spec.bytes + v->X.bytes + v->fr0.bytes + v->fr1.bytes + v->yraw.bytes + v->pw.bytes + v->aws.bytes;
+  return v->spec.bytes + v->X.bytes + v->fr0.bytes + v->fr1.bytes + v->yraw.bytes + v->pw.bytes + v->aws.bytes + v->ymom.bytes;
 }

@@ -160,15 +160,34 @@ __global__ void __launch_bounds__(VOC_THREADS) stft_phase_kernel(const VocGeom g
 // buffer.  `y` is the overlap-added signal of the previous pass (ola_kernel) -- gathering it straight from the frames cost
 // ~4x the loads and ~2 k VALU instructions per frame, and this kernel is VALU-issue bound.  Workgroup w runs on XCD w % 8, so
 // items are dealt out to give each XCD a contiguous run of frames (neighbouring frames share 3/4 of their input in that L2).
+//
+// MOM: the fast Griffin-Lim iteration (Perraudin, Balazs, Soendergaard 2013) in librosa.griffinlim's form.  With
+// beta = momentum / (1 + momentum):
+//   X = S (zero phase);  c_prev = 0
+//   repeat n_iter times:
+//     c      = stft(istft(X))
+//     t      = c - beta * c_prev      (proportional to Perraudin's c + momentum (c - c_prev); only its phase is used)
+//     c_prev = c
+//     X      = S * t / max(1e-8, |t|)
+//   y = istft(X)
+// stft is linear (reflect padding, window and FFT all are), so with y_i = istft(X) of iteration i
+//   t = stft(y_i) - beta * stft(y_{i-1}) = stft(y_i - beta * y_{i-1}):
+// the state is the PREVIOUS PASS'S SIGNAL, hop floats per frame, not a spectrum row of 1025 complex values, and it is
+// already in memory because ola_kernel wrote it.  The momentum form therefore differs from the plain one in its load alone
+// (one more signal, one fma per sample); it stores no state, and the host alternates two signal buffers so that the
+// overlap-add of pass i overwrites y_{i-2}.  The first iteration (c_prev = 0) IS the plain kernel.
+template <bool MOM>
 __device__ __forceinline__ void gl_iter_wave_body(const VocGeom& g, const float* __restrict__ y,
                                                   const float* __restrict__ spec, float* __restrict__ fr_out,
-                                                  int n_items, int per_xcd) {
+                                                  int n_items, int per_xcd, const float* __restrict__ y_prev = nullptr,
+                                                  float beta = 0.f) {
   __shared__ float2 ex[FW_EX];
   const int lane = threadIdx.x;
   const int item = (int)(blockIdx.x & 7) * per_xcd + (int)(blockIdx.x >> 3);
   if ((int)(blockIdx.x >> 3) >= per_xcd || item >= n_items) return;
   const int b = item / g.F, f = item - b * g.F;
   const float* yb = y + (long)b * g.L;
+  const float* ypb = MOM ? y_prev + (long)b * g.L : nullptr;
   const int n0 = f * g.hop - VOC_NFFT / 2;                  // signal index of frame sample 0 (librosa.stft, center=True)
   const int q_lo = g.lpad >> 7, q_hi = (g.lpad + g.win - 1) >> 7;     // lane-strided slots 128 q .. 128 q + 127 that touch the window
   float2 v[16];
@@ -184,7 +203,7 @@ __device__ __forceinline__ void gl_iter_wave_body(const VocGeom& g, const float*
         if (i >= g.lpad && i < g.lpad + g.win) {
           int n = n0 + i;
           if (n < 0) n = -n; else if (n >= g.L) n = 2 * (g.L - 1) - n;      // np.pad(mode="reflect")
-          x = yb[(unsigned)n] * g.window[(unsigned)i];
+          x = (MOM ? fmaf(-beta, ypb[(unsigned)n], yb[(unsigned)n]) : yb[(unsigned)n]) * g.window[(unsigned)i];
         }
         if (h == 0) v[q].x = x; else v[q].y = x;
       }
@@ -242,10 +261,17 @@ __device__ __forceinline__ void gl_iter_wave_body(const VocGeom& g, const float*
 // spills ~34 dwords.  Both are kept so the trade can be measured (DCTTS_VOC_WAVE = 1 | 2).
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 gl_iter_wave_kernel(const VocGeom g, const float* __restrict__ y, const float* __restrict__ spec, float* __restrict__ fr_out,
-                    int n_items, int per_xcd) { gl_iter_wave_body(g, y, spec, fr_out, n_items, per_xcd); }
+                    int n_items, int per_xcd) { gl_iter_wave_body<false>(g, y, spec, fr_out, n_items, per_xcd); }
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 gl_iter_wave4_kernel(const VocGeom g, const float* __restrict__ y, const float* __restrict__ spec, float* __restrict__ fr_out,
-                     int n_items, int per_xcd) { gl_iter_wave_body(g, y, spec, fr_out, n_items, per_xcd); }
+                     int n_items, int per_xcd) { gl_iter_wave_body<false>(g, y, spec, fr_out, n_items, per_xcd); }
+// The momentum form: 164 VGPRs, no scratch.  Under the 4-waves budget it spills 20 dwords and measured 275 us a launch against 210,
+// so only this one is built; DCTTS_VOC_WAVE = 2 selects the plain form's budget alone.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
+gl_iter_wave_mom_kernel(const VocGeom g, const float* __restrict__ y, const float* __restrict__ y_prev, float beta,
+                        const float* __restrict__ spec, float* __restrict__ fr_out, int n_items, int per_xcd) {
+  gl_iter_wave_body<true>(g, y, spec, fr_out, n_items, per_xcd, y_prev, beta);
+}
 
 // grid (ceil(L / 256), B): y (B, L) = istft(X)[n_fft/2 : -n_fft/2] from the stored frames.  The frames that can reach a block of
 // 256 consecutive samples are a block-uniform range (scalar divisions, <= dmax + 2 of them); each lane just tests its index.

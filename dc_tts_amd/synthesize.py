@@ -63,6 +63,8 @@ def main(argv=None):
     ap.add_argument("--out", default="samples")
     ap.add_argument("--save-spectrograms", action="store_true")
     ap.add_argument("--no-wav", action="store_true", help="stop at the magnitude spectrograms (synthesize.py:57)")
+    ap.add_argument("--gl-momentum", type=float, default=0.0, help="fast Griffin-Lim momentum in [0, 1), e.g. 0.99 (librosa's default); 0: the reference's loop")
+    ap.add_argument("--gl-iters", type=int, default=None, help=f"Griffin-Lim iterations (default hp.n_iter = {hp.n_iter})")
     args = ap.parse_args(argv)
     if args.logdir:
         from .tf_checkpoint import load_reference_weights
@@ -80,7 +82,8 @@ def main(argv=None):
     if not args.no_wav:
         from scipy.io.wavfile import write
         from .utils import spectrogram2wav
-        for i, wav in enumerate(spectrogram2wav(Z, hp)):                # synthesize.py:61-64
+        hp_voc = hp if args.gl_iters is None else hp.replace(n_iter=args.gl_iters)
+        for i, wav in enumerate(spectrogram2wav(Z, hp_voc, momentum=args.gl_momentum)):                # synthesize.py:61-64
             write(os.path.join(args.out, f"{i + 1}.wav"), hp.sr, wav)
     print(f"{L.shape[0]} sentences -> {args.out}/ (mel {tuple(Y.shape[1:])}, mag {tuple(Z.shape[1:])}"
           f"{'' if args.no_wav else ', <n>.wav at %d Hz' % hp.sr})")

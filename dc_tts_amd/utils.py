@@ -27,7 +27,7 @@ TRIM_TOP_DB, TRIM_FRAME_LENGTH, TRIM_HOP_LENGTH = 60.0, 2048, 512     # librosa.
 class Vocoder:
     """One vocoder handle per GPU (no weights; workspaces grow to the largest batch seen)."""
 
-    def __init__(self, hp: Hyperparams = _hp, device: Optional[int] = None):
+    def __init__(self, hp: Hyperparams = _hp, device: Optional[int] = None, momentum: float = 0.0):
         if not torch.cuda.is_available():
             raise DcttsError("dc_tts_amd needs a ROCm GPU (torch.cuda.is_available() is False); there is no CPU fallback")
         self.lib = _lib.load()
@@ -39,6 +39,8 @@ class Vocoder:
         h = ctypes.c_void_p()
         self._ok(self.lib.dctts_vocoder_create(ctypes.byref(h), self.device_index, ctypes.byref(cfg)))
         self._h = h
+        if momentum != 0.0:
+            self.set_momentum(momentum)
 
     def _ok(self, rc: int):
         if rc != 0:
@@ -60,6 +62,10 @@ class Vocoder:
 
     def device_bytes(self) -> int:
         return int(self.lib.dctts_vocoder_device_bytes(self._h))
+
+    def set_momentum(self, momentum: float):
+        """Fast Griffin-Lim as librosa.griffinlim(momentum=...), 0 <= momentum < 1, from the next call on; 0 (the default) is the reference's loop."""
+        self._ok(self.lib.dctts_vocoder_set_momentum(self._h, float(momentum)))
 
     def prof_enable(self, enable: bool):
         self._ok(self.lib.dctts_vocoder_prof_enable(self._h, int(bool(enable))))
@@ -133,11 +139,18 @@ class Vocoder:
 _default: dict = {}
 
 
-def _vocoder(hp: Hyperparams, device: Optional[int]) -> Vocoder:
-    key = (hp, torch.cuda.current_device() if device is None and torch.cuda.is_available() else device)
+def _vocoder(hp: Hyperparams, device: Optional[int], momentum: Optional[float] = None) -> Vocoder:
+    """The cached handle per (hp, device, momentum): a call that passes `momentum` never changes what a call without it computes."""
+    key = (hp, torch.cuda.current_device() if device is None and torch.cuda.is_available() else device, float(momentum or 0.0))
     if key not in _default:
-        _default[key] = Vocoder(hp, device)
+        _default[key] = Vocoder(hp, device, momentum=key[2])
     return _default[key]
+
+
+def _pick(hp: Hyperparams, vocoder: Optional[Vocoder], momentum: Optional[float]) -> Vocoder:
+    if vocoder is not None and momentum is not None:
+        raise ValueError("pass either a Vocoder (its own momentum holds) or momentum=, not both")
+    return vocoder or _vocoder(hp, None, momentum)
 
 
 def _to_dev(a, device: torch.device) -> Tuple[torch.Tensor, bool]:
@@ -148,10 +161,10 @@ def _to_dev(a, device: torch.device) -> Tuple[torch.Tensor, bool]:
     return t.to(device=device, dtype=torch.float32).contiguous(), single
 
 
-def spectrogram2wav(mag, hp: Hyperparams = _hp, vocoder: Optional[Vocoder] = None):
+def spectrogram2wav(mag, hp: Hyperparams = _hp, vocoder: Optional[Vocoder] = None, momentum: Optional[float] = None):
     """utils.py:67-94.  mag: (T, 1+n_fft//2) -> 1-D float32 numpy waveform (trimmed), as the reference returns it;
-    or a batch (B, T, 1+n_fft//2) (numpy or torch) -> list of B such waveforms."""
-    v = vocoder or _vocoder(hp, None)
+    or a batch (B, T, 1+n_fft//2) (numpy or torch) -> list of B such waveforms.  momentum: fast Griffin-Lim (Vocoder.set_momentum)."""
+    v = _pick(hp, vocoder, momentum)
     m, single = _to_dev(mag, v.device)
     wav, bounds = v.spectrogram2wav_device(m)
     wav_h, b_h = wav.cpu().numpy(), bounds.cpu().numpy()
@@ -199,9 +212,9 @@ def load_spectrograms(fpath_or_list, hp: Hyperparams = _hp, vocoder: Optional[Vo
     return out[0] if single else out
 
 
-def griffin_lim(spectrogram, hp: Hyperparams = _hp, vocoder: Optional[Vocoder] = None):
-    """utils.py:96-106, on (T, 1+n_fft//2) magnitudes (or a batch): returns the real waveform(s) as numpy."""
-    v = vocoder or _vocoder(hp, None)
+def griffin_lim(spectrogram, hp: Hyperparams = _hp, vocoder: Optional[Vocoder] = None, momentum: Optional[float] = None):
+    """utils.py:96-106, on (T, 1+n_fft//2) magnitudes (or a batch): returns the real waveform(s) as numpy.  momentum: as spectrogram2wav."""
+    v = _pick(hp, vocoder, momentum)
     s, single = _to_dev(spectrogram, v.device)
     y = v.griffin_lim_device(s).cpu().numpy()
     return y[0] if single else y

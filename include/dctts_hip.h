@@ -214,6 +214,15 @@ int dctts_spectrogram2wav(dctts_vocoder* v, const float* mag, int B, int F, floa
  * iteration produced (needs n_iter >= 1).  n_iter = 0 gives y = istft(spec). */
 int dctts_griffin_lim(dctts_vocoder* v, const float* spec, int B, int F, int n_iter, float* y, float* X_best, void* stream);
 
+/* Fast Griffin-Lim (Perraudin, Balazs, Soendergaard 2013) in the form of librosa.griffinlim(momentum=...): with
+ * beta = momentum / (1 + momentum) every iteration projects the phase of  t = c - beta * c_prev  instead of that of
+ * c = stft(istft(X)), c_prev = 0 in the first.  0 <= momentum < 1, anything else (NaN too) is DCTTS_ERR_ARG; 0, the
+ * default, is the reference's loop (utils.py:96-106), bit for bit.  Holds for dctts_spectrogram2wav and
+ * dctts_griffin_lim from the next call on.  A non-zero momentum costs one more signal buffer (B, hop_length*(F-1))
+ * floats, counted by dctts_vocoder_device_bytes once a call with n_iter >= 2 has used it; X_best != NULL together
+ * with it is DCTTS_ERR_ARG.  Results stay bitwise reproducible and independent of the rest of the batch. */
+int dctts_vocoder_set_momentum(dctts_vocoder* v, float momentum);
+
 /* The analysis direction: utils.py:18-65 get_spectrograms and the frame reduction of load_spectrograms (:155-164) for a RAGGED batch of waveforms.
  * dctts_vocoder_set_mel_basis: basis_host (n_mels, 1 + n_fft/2) row-major on the HOST, what librosa.filters.mel returns; packed once into a band table
  * (first bin, width) + the non-zero weights and uploaded.  DCTTS_ERR_ARG if a row's non-zeros are not one contiguous run, a band is wider than 96 bins
