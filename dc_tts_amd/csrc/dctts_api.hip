@@ -19,6 +19,7 @@
 #include "../../include/dctts_hip.h"
 #include "../../include/dctts_hip_debug.h"
 #include "api_common.h"
+#include "decode_form.h"
 #include "attn_kernels.h"
 #include "decode_kernels.h"
 #include "decode_fallback_kernels.h"
@@ -266,28 +267,12 @@ struct dctts_ctx {
   std::vector<hipGraphExec_t> bulk3_g; std::string graphs3_geom;   // one small linear graph per frame for the side stream, frame index baked into every launch
   void* aepre_tab = nullptr; std::string aepre_geom; int aepre_layers = 0;
   void* mlp_tab = nullptr; std::string mlp_geom;
-  // How the chain runs AudioDec behind C_1 (DCTTS_CHAIN_TAIL): 2 (default) = xtail_kernel, merged form: the newest-row layers HC_2 .. HC_4, HC_5 .. HC_7 over the
-  // few cone rows they need and the seven k = 1 layers around the mel frame, ONE launch in team form (the side stream stops behind HC_4); 5 = the same with
-  // HC_2 .. HC_4 as an xgroup_kernel launch in front; 1 = xmlp_kernel: the seven k = 1 layers in team form (HC_5 .. HC_7 stay split between the chain's run
-  // and the side stream); 0 = mlp_rows_kernel (round 2: split by rows); 3 / 4: A/B forms (tools/README.md)
-  int chain_tail = 2; bool tail_on = false, xmlp_on = false;
-  int tail_np = 4, np_eff = 3;         // round 6 (DCTTS_CHAIN_TAIL=7 selects 3): newest-row layers in front of the chain launch's cone layers: 4 = HC_2 .. HC_5 (HC_5's older cone rows on the side stream: xcone_kernel runs HC_3 .. HC_5),
-                                       //   3 = rounds 4-5 (HC_2 .. HC_4; the side stream stops behind HC_4); np_eff: what this decode uses (the merged forms only)
-  int team_u = 4;                      // utterances per team and round of THIS decode (decode_host.h: team_u_for); DCTTS_XGROUP=2 = the team kernels with four whatever the batch (A/B, tests)
-  bool chain_one = false;              // round 5 (chain_tail == 2): a chain piece is ONE launch -- xtail_kernel's layers, a team barrier, the AudioEnc run + attention + C_1 (xchain_kernel); 6: two launches (round 4)
-  bool dec_merge = false;              // chain_tail == 2: AudioDec's newest-row layers HC_2 .. HC_4 run in FRONT of xtail_kernel's cone layers in the same launch (chain_tail 2 and 6)
-  bool ae_pass_split = false;          // round 4: AudioEnc's presums ride in the PREVIOUS piece's AudioEnc launch (a row ahead), only the C1Q . W2 row stays in the AudioDec launch
-  bool side_fold = true;               // round 5: rowc1 / rowhc2 as the first phases of xcone_kernel's launch (DCTTS_XCONE=2: three launches per side-stream piece, rounds 3-4)
-  bool side_pre = false;               // the small presum GEMMs (AudioEnc's presums of the next row, the newest C1Q . W2 row) run on the SIDE stream, which has the slack since xtail_kernel (round 4), instead of as passenger workgroups of the chain's AudioDec launch
-  bool attn_fold = false;              // the newest row's attention + AudioDec C_1 run behind the AudioEnc run's last layer inside xgroup_kernel (chain_tail >= 1) instead of as two more launches
+  // Which launch form a decode takes (decode_form.h): what was asked for, what this context can do (xgroup_ok, can_stream_wait_value; decode_caps adds the rest per
+  // decode), and the running decode's resolved form -- set once at the top of decode_v3, read-only below it
+  DecodeKnobs knobs; DecodeCaps caps; DecodeForm form;
   void* xmlp_tab = nullptr; std::string xmlp_geom;
   void* xtail_tab = nullptr; std::string xtail_geom;
-  // runs of chain highway layers as one launch whose workgroups meet inside one XCD (xgroup_kernel.h); DCTTS_XGROUP=0: one launch per layer
-  int xgroup = 1;
-  bool ae_pass = false; int xg_T = 0;  // AudioEnc's presums and the C1Q . W2 row ride in the AudioDec run's xgroup_kernel launch (passengers); frames of the xgroup table
-  bool c1qw_chain = false;             // the C1Q . W2 row rides in the chain's AudioEnc presum launch (decode_v3)
-  bool xg_on = false, xc_on = false;   // this decode uses them
-  bool xgroup_ok = true;               // cleared for good when a decode reports that the placement assumption (block b on XCD b % 8) does not hold here
+  int xg_T = 0;                        // frames of the xgroup table
   void* xg_tab = nullptr; std::string xg_geom;   // per chain piece: [T + 1][2] XGroupParams (AudioDec run of frame j, AudioEnc run of frame j + 1)
   float* xg_mem = nullptr;             // exchange buffers (2 networks x 2 parity copies of rows + statistics), team barriers, error word: one allocation
   // Decode status (decode_host.h: decode_finish): the LAST kernel of every decode folds that decode's error words (team kernels, in-kernel waits, the
@@ -300,21 +285,15 @@ struct dctts_ctx {
   int team_fail_streak = 0;            // consecutive failed status reports without a split-team bit: the team kernels are switched off at 3
   std::thread::id safe_once_tid;       // ... requested by this host thread: only a decode call of the same thread consumes it (another thread's decode in between keeps the team kernels)
   bool safe_once = false;              // dctts_decode_safe_once: the NEXT decode runs one launch per layer with stream-operation meetings, then the settings are as before
-  // the tail of AudioDec's cone (HC_3 .. HC_7 and their row passes) as one launch per frame on the side stream (xcone_kernel.h); DCTTS_XCONE=0: nine launches
-  int xcone = 1;
   void* xc_tab = nullptr; std::string xc_geom;   // per frame: XConeParams
   hipStream_t s_bulk = nullptr; hipEvent_t ev_fork = nullptr;
   unsigned* conc_flags = nullptr; int stream_retries = 0;       // decode_streams_init: the two decode streams are TESTED for running concurrently (decode_host.h); side streams rejected on the way
   hipStream_t own_tested = nullptr; bool own_ok = false;        // the last caller's high-priority stream tested against the side stream, and the result
   hipStream_t s_chain = nullptr; hipEvent_t ev_in = nullptr, ev_out = nullptr;      // decode mode 3: the chain's launches run on a high-priority stream of the context between two events on the caller's stream (decode_host.h)
   hipEvent_t ev_chain[4] = {nullptr, nullptr, nullptr, nullptr}, ev_bulk[4] = {nullptr, nullptr, nullptr, nullptr};
-  int sync_values = 1;                 // the two streams meet through stream memory operations (hipStreamWriteValue32 / WaitValue32 on two counters) instead of events
-                                       // (DCTTS_SYNC_VALUES=0; rocprofv3 --pmc needs events: read_env)
   uint32_t* ctr_chain = nullptr; uint32_t* ctr_bulk = nullptr;   // signal memory: chain pieces done + 1, bulk pieces done
   unsigned* sig_ptr = nullptr;         // ... the counter itself: signal memory (stream wait operations on the side stream) or wait_ctr[0] (the side stream polls in-kernel)
   unsigned sig_next = 0;               // value the next run_chain3 launch writes to the chain's counter (0 = none)
-  int chain_wait_inkernel = 1;         // the chain's wait for the bulk's counter happens inside the piece's first launch (sc1 read of the one operand the bulk
-                                       // produced for it) instead of a wait-value operation in front of it (DCTTS_CHAIN_WAIT=0)
   unsigned wait2_next = 0;             // counter value the next run_chain3 launch waits for (0 = none)
   unsigned* wait_ctr = nullptr;        // device memory, polled in-kernel: [0] chain pieces done + 1, [32] bulk pieces complete (written by xcone_kernel's last team, or a write-value operation), [64] error word
   hipGraph_t graph = nullptr; hipGraphExec_t graph_exec = nullptr; std::string graph_geom;   // decode mode 0: one step, replayed T times
@@ -598,14 +577,17 @@ static std::vector<std::vector<int>> audiodec_cone(const std::vector<DevLayer>& 
 // Measurement / A-B knobs (tools/README.md).  Read once per context: the decode path itself never calls getenv.
 static void read_env(dctts_ctx* c) {
   auto geti = [](const char* n, int* v) { if (const char* e = getenv(n)) *v = atoi(e); };
-  geti("DCTTS_SYNC_VALUES", &c->sync_values); geti("DCTTS_CHAIN_WAIT", &c->chain_wait_inkernel); geti("DCTTS_XGROUP", &c->xgroup); geti("DCTTS_XCONE", &c->xcone); geti("DCTTS_CHAIN_TAIL", &c->chain_tail);
+  DecodeKnobs& k = c->knobs;
+  int ct = (int)k.chain_tail;
+  geti("DCTTS_SYNC_VALUES", &k.sync_values); geti("DCTTS_CHAIN_WAIT", &k.chain_wait_inkernel); geti("DCTTS_XGROUP", &k.xgroup); geti("DCTTS_XCONE", &k.xcone); geti("DCTTS_CHAIN_TAIL", &ct);
   geti("DCTTS_TRACE", &c->trace_frame);
   geti("DCTTS_PIECETIME", &c->piecetime);
-  if (c->chain_tail == 7) { c->chain_tail = 2; c->tail_np = 3; }      // 7 = the default form with round 5's split of the cone (A/B)
+  if (chain_tail_known(ct)) k.chain_tail = (ChainTail)ct;
+  else fprintf(stderr, "[dctts] DCTTS_CHAIN_TAIL=%d names no decode form (0, 1, 2, 5, 6, 7: tools/README.md): the default runs\n", ct);
   if (const char* e = getenv("DCTTS_TRACE_FILE")) c->trace_file = e;
   // rocprofv3 --pmc serialises dispatches ACROSS queues: a launch that polls the other stream's counter would never see it move
   // (it only times out, with wrong results).  Under counter collection the two decode streams meet through events instead.
-  if (const char* e = getenv("ROCPROF_COUNTER_COLLECTION")) { if (atoi(e) != 0 && !getenv("DCTTS_SYNC_VALUES")) c->sync_values = 0; }
+  if (const char* e = getenv("ROCPROF_COUNTER_COLLECTION")) { if (atoi(e) != 0 && !getenv("DCTTS_SYNC_VALUES")) k.sync_values = 0; }
 }
 
 // ------------------------------------------------------------------------------------------------ C ABI: lifetime
@@ -623,6 +605,9 @@ extern "C" int dctts_create(dctts_ctx** out, int device, const dctts_config* cfg
   if (!dev_guard.ok) { delete c; return fail(DCTTS_ERR_HIP, "hipSetDevice: no such device"); }
   int ncu = 0;
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->n_cu = ncu;
+  int can = 0;                          // stream memory operations (the decode's counters); without them the streams meet through events
+  (void)hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device);
+  c->caps.can_stream_wait_value = can != 0;
   read_env(c);
   {
     size_t fr = 0, tot = 0;

@@ -225,6 +225,9 @@ static int streams_run_concurrently(dctts_ctx* c, hipStream_t a, hipStream_t b, 
   return 0;
 }
 
+// DecodeForm::counters for the code in front of decode_v3 (it depends on neither the batch nor the networks; a safe-once decode leaves it alone)
+static inline bool meets_through_counters(const dctts_ctx* c) { return resolve_decode_form(c->knobs, c->caps, 1).counters; }
+
 static int decode_streams_init(dctts_ctx* c) {
   if (c->s_bulk) return 0;
   {
@@ -247,7 +250,7 @@ static int decode_streams_init(dctts_ctx* c) {
     int rc = 0;
     // (not when the streams meet through EVENTS only -- DCTTS_SYNC_VALUES=0, what rocprofv3 --pmc selects: counter collection runs dispatches one at a time across
     //  all queues, the test could only fail there, and event meetings need no concurrency)
-    if (!c->sync_values) ok = true;
+    if (!meets_through_counters(c)) ok = true;
     for (int attempt = 0; attempt < 8 && !ok; ++attempt) {
       rc = streams_run_concurrently(c, c->s_chain, c->s_bulk, &ok);
       if (rc != 0 || ok) break;
@@ -325,8 +328,8 @@ static void drop_decode_tables(dctts_ctx* c) {      // (the caller has synchroni
 //     AudioEnc presums for row f (one grouped launch) | C_1 cone rows (rowc1_kernel) | per k=3 AudioDec layer: cone rows + the
 //     presum row of frame f in one GEMM, then LN / gate of the cone rows.
 static inline int aepre_stride(const dctts_ctx* c) { return c->aepre_layers + 3; }      // descriptors per parity copy of the table (v3_aepre_table)
-static int v3_aepre_table(dctts_ctx* c, const DecodeWs& w, int B, bool c1qw_ahead) {
-  const std::string g = std::to_string(B) + ":" + std::to_string((int)c1qw_ahead) + ":" + std::to_string((size_t)w.ae[0].p) + ":" + std::to_string((size_t)w.pse.back()) + ":" + std::to_string((size_t)w.c1qw.p) + ":" + std::to_string((int)c->chain_one);
+static int v3_aepre_table(dctts_ctx* c, const DecodeWs& w, int B) {
+  const std::string g = std::to_string(B) + ":" + c->form.key() + ":" + std::to_string((size_t)w.ae[0].p) + ":" + std::to_string((size_t)w.pse.back()) + ":" + std::to_string((size_t)w.c1qw.p);
   if (c->aepre_tab && c->aepre_geom == g) return 0;
   { dctts_ctx::TabSlot ts; if (tab_lookup(c, "aepre", g, &ts)) { c->aepre_tab = ts.tab; c->aepre_layers = ts.n0; c->aepre_geom = g; return 0; } }
   std::vector<SplitParams> tab;
@@ -353,8 +356,8 @@ static int v3_aepre_table(dctts_ctx* c, const DecodeWs& w, int B, bool c1qw_ahea
           h.ntaps = 2; h.tap_off[0] = h.tap_off[1] = -2; h.cin = H.cin; h.cin_p = H.cin_p;
           h.wp = H.wp; h.bias = H.bias; h.cout = H.cout; h.hc = 1; h.np_out = 6 * H.cout; h.pout = w.c1qw.p + (long)q * 2 * H.cout;
           h.abs_bstride = w.c1qw.bstride; h.abs_row0 = w.c1qw.row0; h.abs_toff = -2;
-          h.step_val = (c1qw_ahead && !c->chain_one) ? 1 : 0;       // launched from the chain's stream, one piece earlier (decode_v3): the row is the chain's newest C1Q row
-                                                                    // (chain_one: the passengers' step is already one further: they compute AudioEnc's presums of row j + 2)
+          h.step_val = (c->form.c1qw_on_chain && !c->form.one_launch) ? 1 : 0;       // launched from the chain's stream, one piece earlier (decode_v3): the row is the chain's newest C1Q row
+                                                                                     // (one_launch: the passengers' step is already one further: they compute AudioEnc's presums of row j + 2)
           tab.push_back(h);
         }
         // ... and the same three once more without the zero half of K (K = 256, hbulk_body<4>): xtail_kernel's passengers run these -- side-stream piece j + 1
@@ -416,7 +419,7 @@ static RowC1Params fill_rowc1(dctts_ctx* c, const DecodeWs& w, int B, int N, int
   q.N = N; q.d = d; q.win = c->cfg.attention_win_size; q.pm_all = w.pm_all;
   q.x = w.ad[0].p; q.x_bstride = w.ad[0].bstride; q.x_row0 = w.ad[0].row0; q.x_stride = w.ad[0].stride; q.x_set = w.ad[0].set;
   q.scal = w.scal.p; q.s_bstride = w.scal.bstride; q.s_row0 = w.scal.row0;
-  if (c->ae_pass && f > 0) { q.wait = c->wait_ctr + 16; q.wait_val = (unsigned)f; q.wait_err = (int*)(c->wait_ctr + 64); }      // row f - 1 of the C1Q . W2 cache: passengers of chain piece f - 1
+  if (c->form.passengers && f > 0) { q.wait = c->wait_ctr + 16; q.wait_val = (unsigned)f; q.wait_err = (int*)(c->wait_ctr + 64); }      // row f - 1 of the C1Q . W2 cache: passengers of chain piece f - 1
   q.contig = c->cone_contig[0];
   return q;
 }
@@ -447,8 +450,8 @@ static int v3_bulk_rest(dctts_ctx* c, const DecodeWs& w, int B, int N, int T, in
   // the C1Q . diag(gamma1) W2 cache that rowhc2_kernel reads below
   // (with the team kernels the side stream is the longer one: AudioEnc's presums then run on the chain's stream, in front of the piece that uses them)
   // (wait_val != 0: the launch first polls the chain's counter for that value -- the piece's input row comes from the chain's stream)
-  if (!c->c1qw_chain) CHK(v3_aepre(c, B, f + 1, sb, c->xc_on ? 2 : 0, wait_val));
-  const bool fold = c->xc_on && c->side_fold;            // round 5: both row operations are the first phases of xcone_kernel's launch (its per-frame table carries their parameters)
+  if (!c->form.c1qw_on_chain) CHK(v3_aepre(c, B, f + 1, sb, c->form.xcone_on ? 2 : 0, wait_val));
+  const bool fold = c->form.side_fold;                   // round 5: both row operations are the first phases of xcone_kernel's launch (its per-frame table carries their parameters)
   if (c->cone_len[0] > 1 && !fold) {
     const RowC1Params q = fill_rowc1(c, w, B, N, f);
     hipLaunchKernelGGL(rowc1_kernel, dim3((q.R + ROWC1_NW - 1) / ROWC1_NW, B), dim3(ROWC1_NW * 64), 0, sb, q);
@@ -464,15 +467,14 @@ static int v3_bulk_rest(dctts_ctx* c, const DecodeWs& w, int B, int N, int T, in
     }
     first_gemm = 2;
   }
-  if (c->side_pre && f + 1 < T) CHK(v3_aepre(c, B, f + 1, sb, 1));      // AudioEnc's presums of row f + 1 (inputs: rows <= f - 1): consumed by the AudioEnc run of chain piece f, which starts behind this piece
-  if (c->xc_on) {                                        // HC_3 .. HC_7 and their row passes: one launch, teams inside one XCD (xcone_kernel.h)
+  if (c->form.xcone_on) {                                       // HC_3 .. HC_7 and their row passes: one launch, teams inside one XCD (xcone_kernel.h)
     const XConeParams* xp = (const XConeParams*)c->xc_tab + f;
     const bool prof = c->prof_id == DCTTS_PROF_XCONE && f >= 100 && (f & 15) == 8;          // full-size cones only; eager decode only (graph mode 0)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, sb)); }
     hipLaunchKernelGGL(xcone_kernel, dim3(128), dim3(512), 0, sb, xp, (const int*)(w.pm_all + (long)f * B));
     HIPCHK(hipGetLastError());
-    if (prof) { HIPCHK(hipEventRecord(e1, sb)); c->prof_ev.emplace_back(e0, e1); c->prof_cnt.push_back(1); long rows = 0; for (size_t i = 2; i < (c->tail_on ? (size_t)(c->np_eff + 1) : AD.size()); ++i) if (AD[i].hc) rows += (long)B * c->cone_len[i]; c->prof_rows += rows; }
+    if (prof) { HIPCHK(hipEventRecord(e1, sb)); c->prof_ev.emplace_back(e0, e1); c->prof_cnt.push_back(1); long rows = 0; for (size_t i = 2; i < (c->form.xtail_on ? (size_t)(c->form.np + 1) : AD.size()); ++i) if (AD[i].hc) rows += (long)B * c->cone_len[i]; c->prof_rows += rows; }
     return 0;
   }
   for (size_t i = first_gemm; i < AD.size(); ++i) {
@@ -565,20 +567,12 @@ static int run_chain3(dctts_ctx* c, const DevLayer& L, int B, int j, const DevLa
 }
 
 
-
-// Utterances per team and round (round 6).  Rounds 3-5: always four -- a batch of 8 then ran on two of the eight teams (XCDs) while six idled, and the frame cost what
-// it costs at B = 32.  Now a batch of at most 8 / 16 is dealt one / two utterances to a team, so that all eight teams work (the side stream's cone GEMMs and row phases
-// shrink with the rows a team owns; the chain's latency-bound layers do not).  The arithmetic of an utterance does not depend on the slot it sits in: results are bitwise
-// those of the four-utterance form (DCTTS_XGROUP=2 forces it: tests).  Only the forms whose three team kernels all know about it (the merged chain forms).
-static inline int team_u_for(const dctts_ctx* c, int B) {
-  if (!c->dec_merge || c->xgroup == 2) return 4;
-  return B > 16 ? 4 : (B > 8 ? 2 : 1);
-}
+// rounds of eight teams that a batch takes at U utterances per team and round (DecodeForm::team_u)
 static inline int team_rounds(int B, int U) { return ((B + U - 1) / U + 7) / 8; }
 
 // ---- xgroup_kernel plumbing: one XGroupParams per (chain piece, network) in device memory; exchange buffers + team barriers + error word
 struct XgMem { float* xch[2]; float* sch[2]; float* xch_m; float* sch_m; float* xch_h; float* sch_h; unsigned* bar; unsigned* bar_cone; unsigned* bar_mlp; int* err; int bpad; size_t bar_words; };
-static inline int xg_hgroups(int B) { const int bpad = (B + 3) / 4 * 4; return B <= 16 ? bpad : bpad / 4; }      // utterance groups of xtail_kernel's highway exchange: one per utterance when a small batch is dealt singly (team_u_for)
+static inline int xg_hgroups(int B) { const int bpad = (B + 3) / 4 * 4; return B <= 16 ? bpad : bpad / 4; }      // utterance groups of xtail_kernel's highway exchange: one per utterance when a small batch is dealt singly (DecodeForm::team_u)
 static size_t xg_mem_floats(int B) { const int bpad = (B + 3) / 4 * 4; return (size_t)2 * (2 * bpad * 512 + 2 * bpad * 64) + (size_t)(2 * bpad * 512 + 2 * bpad * 64) + (size_t)2 * xg_hgroups(B) * XT_MAXM * (512 + 64) + (size_t)3 * ((bpad / 4 + 7) / 8 * 8) * 32 + 64; }
 static XgMem xg_mem(dctts_ctx* c, int B) {
   XgMem m; m.bpad = (B + 3) / 4 * 4;
@@ -597,10 +591,10 @@ static XgMem xg_mem(dctts_ctx* c, int B) {
 // Chain piece j (j = -1 .. T-1) launches, in this order: the AudioDec run of frame j (j >= 0; since the merged form of round 4 the front of xtail_kernel's
 // launch, v3_xtail_table, and not launched from this table), ..., the AudioEnc run of frame j + 1 (j + 1 < T).
 // The team barriers count arrivals monotonically over the whole decode, so every launch is told the count it starts from.
-static int v3_xgroup_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool insig, bool cwait) {
-  const std::string g = geom("xg", B, T) + ":" + std::to_string((size_t)w.pe[0]) + ":" + std::to_string((size_t)w.ae[0].p) + ":" + std::to_string((size_t)w.pb3[1]) + ":" + std::to_string((size_t)w.ad[0].p) + ":" +
-                        std::to_string((int)insig) + ":" + std::to_string((int)cwait) + ":" + std::to_string((size_t)c->sig_ptr) + ":" + std::to_string((size_t)c->wait_ctr) + ":" +
-                        std::to_string((size_t)c->aepre_tab) + ":" + std::to_string((int)c->ae_pass) + ":" + std::to_string((int)c->ae_pass_split) + ":" + std::to_string(c->trace_frame) + ":" + std::to_string((int)c->tail_on) + ":" + std::to_string((int)c->dec_merge) + ":" + std::to_string((int)c->attn_fold) + ":" +
+static int v3_xgroup_table(dctts_ctx* c, const DecodeWs& w, int B, int T) {
+  const DecodeForm& fm = c->form;
+  const std::string g = geom("xg", B, T) + ":" + fm.key() + ":" + std::to_string((size_t)w.pe[0]) + ":" + std::to_string((size_t)w.ae[0].p) + ":" + std::to_string((size_t)w.pb3[1]) + ":" + std::to_string((size_t)w.ad[0].p) + ":" +
+                        std::to_string((size_t)c->sig_ptr) + ":" + std::to_string((size_t)c->wait_ctr) + ":" + std::to_string((size_t)c->aepre_tab) + ":" + std::to_string(c->trace_frame) + ":" +
                         std::to_string((size_t)w.kv.p) + ":" + std::to_string((size_t)w.vw) + ":" + std::to_string((size_t)w.c1q.p) + ":" + std::to_string((size_t)w.pm_all);
   if (c->xg_tab && c->xg_geom == g) return 0;
   { dctts_ctx::TabSlot ts; if (tab_lookup(c, "xg", g, &ts)) { c->xg_tab = ts.tab; c->xg_mem = (float*)ts.mem; c->xg_T = ts.n0; c->xg_geom = g; return 0; } }
@@ -621,10 +615,10 @@ static int v3_xgroup_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool i
       const std::vector<DevLayer>& Lr = net ? AE : AD;
       size_t i0 = 0; while (i0 < Lr.size() && !Lr[i0].hc) ++i0;
       size_t i1 = i0; while (i1 < Lr.size() && Lr[i1].hc) ++i1;
-      if (net == 0 && c->tail_on) i1 = i0 + 3;                 // AudioDec HC_2 .. HC_4 only: HC_5 .. HC_7 run in xtail_kernel, the launch behind this one
+      if (net == 0 && fm.xtail_on) i1 = i0 + 3;                 // AudioDec HC_2 .. HC_4 only: HC_5 .. HC_7 run in xtail_kernel, the launch behind this one
       const int L = (int)(i1 - i0);
       if (i0 == 0 || L < 2 || L > 10 || Lr[i0 - 1].cout != 256 || Lr[i0 - 1].act != ACT_NONE) return fail(DCTTS_ERR_STATE, "xgroup: a run of 2..10 highway layers after a linear 256-channel layer");
-      p.B = B; p.L = L; p.U = c->team_u;
+      p.B = B; p.L = L; p.U = fm.team_u;
       const std::vector<float*>& P = net ? w.pe : w.pd; const std::vector<float*>& S = net ? w.se : w.sd;
       const std::vector<View>& H = net ? w.ae : w.ad;
       p.P0 = P[i0 - 1]; p.p0_bs = 256; p.stats0 = S[i0 - 1]; p.pg1 = Lr[i0 - 1].g1; p.pb1 = Lr[i0 - 1].b1;
@@ -644,7 +638,7 @@ static int v3_xgroup_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool i
       p.pout = P[i1 - 1]; p.stats_out = S[i1 - 1];
       p.xch = m.xch[net]; p.sch = m.sch[net]; p.xch_set = m.bpad * 512; p.sch_set = m.bpad * 64;
       p.bar = m.bar; p.bar_base = arrivals; p.err = m.err;
-      if (net == 1 && c->attn_fold) {
+      if (net == 1 && fm.attn_fold) {
         // the attention row of frame j and AudioDec C_1 of frame j behind the run's last layer (what attnq_kernel + chain3_kernel<RAW> compute, v3_chain_enc)
         const size_t la = AE.size() - 1;
         const int d = c->cfg.d;
@@ -656,29 +650,19 @@ static int v3_xgroup_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool i
         p.c1_raw = w.c1q.p + (w.c1q.row0 + j) * (long)w.c1q.stride; p.raw_bs = (int)(w.c1q.bstride * w.c1q.stride);
         p.c1_pout = w.pd[0]; p.c1_stats = w.sd[0];
       }
-      if (!(net == 0 && c->dec_merge))                          // (merged form: the AudioDec run is part of xtail_kernel's launch, which has barrier words of its own)
-        arrivals += (unsigned)team_rounds(B, c->team_u) * (unsigned)(L - 1 + p.attn) * 16u;      // (a team with more than one utterance group runs them in turn: xgroup_kernel.h)
+      if (!(net == 0 && fm.dec_merged))                          // (merged form: the AudioDec run is part of xtail_kernel's launch, which has barrier words of its own)
+        arrivals += (unsigned)team_rounds(B, fm.team_u) * (unsigned)(L - 1 + p.attn) * 16u;      // (a team with more than one utterance group runs them in turn: xgroup_kernel.h)
       if (net == 0) {                                           // the first launch of chain piece j: publishes the chain's counter and waits for bulk piece j
-        if (insig) { p.sig = c->sig_ptr; p.sig_val = (unsigned)(j + 1); }
-        if (cwait) { p.wait2 = c->wait_ctr + 32; p.wait_val = (unsigned)(j + 1); }
-        if (c->ae_pass && j + 1 < T) {
+        if (fm.chain_signals_inkernel) { p.sig = c->sig_ptr; p.sig_val = (unsigned)(j + 1); }
+        if (fm.chain_waits_inkernel) { p.wait2 = c->wait_ctr + 32; p.wait_val = (unsigned)(j + 1); }
+        if (fm.passengers && j + 1 < T) {
           // passengers: AudioEnc's presums of row j + 1 (inputs: rows <= j - 1; the AudioEnc run of frame j + 1 follows on this stream) and row j of
           // the C1Q . W2 cache (the table's last three descriptors), which side-stream piece j + 1 needs behind its first launch.
-          // Round 4 (ae_pass_split): only those three descriptors ride here -- 24 workgroups find CUs between the side stream's row kernels at once, 104
-          // found them only when this launch's teams had finished (~4 us on the chain); AudioEnc's presums ride in the PREVIOUS piece's AudioEnc launch.
           const int ipl = ((B + 31) / 32) * (c->cfg.d / 32);
-          const int first = c->ae_pass_split ? c->aepre_layers - 3 : 0;
-          p.ptab = (const SplitParams*)c->aepre_tab + (size_t)((j + 1) & 1) * aepre_stride(c) + first;
-          p.p_ipl = ipl; p.p_blocks = (c->aepre_layers - first) * ipl; p.p_step = j + 1; p.p_count_from = c->aepre_layers - 3 - first;
+          p.ptab = (const SplitParams*)c->aepre_tab + (size_t)((j + 1) & 1) * aepre_stride(c);
+          p.p_ipl = ipl; p.p_blocks = c->aepre_layers * ipl; p.p_step = j + 1; p.p_count_from = c->aepre_layers - 3;
           p.pdone = (unsigned*)m.err + 2; p.pdone_target = (unsigned)(j + 1) * (unsigned)(3 * ipl); p.psig = c->wait_ctr + 16; p.psig_val = (unsigned)(j + 1);
         }
-      } else if (c->ae_pass && c->ae_pass_split && j + 1 < T) {
-        // the AudioEnc run of frame j (launched in chain piece j - 1) carries AudioEnc's presums of row j + 1: their inputs are rows <= j - 1, final since chain
-        // piece j - 2, and their consumer is the AudioEnc run of frame j + 1, a later launch on this stream.  They start when the side stream's xcone_kernel
-        // lets go of its CUs (~15 us before this launch ends) and are done before it.
-        const int ipl = ((B + 31) / 32) * (c->cfg.d / 32);
-        p.ptab = (const SplitParams*)c->aepre_tab + (size_t)((j + 1) & 1) * aepre_stride(c);
-        p.p_ipl = ipl; p.p_blocks = (c->aepre_layers - 3) * ipl; p.p_step = j + 1; p.p_count_from = c->aepre_layers - 3;      // (none of them is counted)
       }
       if (c->trace_frame >= 0 && piece == c->trace_frame) {     // DCTTS_TRACE: this piece's two launches record their phase boundaries (unset = -1, which is also the first piece's index)
         if (!c->trace_buf) { HIPCHK(hipMalloc((void**)&c->trace_buf, 64 * 64 * 32 * sizeof(long long))); HIPCHK(dev_zero_now(c->trace_buf, 64 * 64 * 32 * sizeof(long long))); }
@@ -704,8 +688,7 @@ static int v3_xgroup_launch(dctts_ctx* c, int B, int piece, int net, hipStream_t
   if (prof) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, st)); }
   const int ipl_ = ((B + 31) / 32) * (c->cfg.d / 32);
   int pass = 0;                                                                                                     // passenger workgroups, as in the table
-  if (net == 0 && c->ae_pass && piece >= 0 && piece + 1 < c->xg_T) pass = (c->ae_pass_split ? 3 : c->aepre_layers) * ipl_;
-  if (net == 1 && c->ae_pass && c->ae_pass_split && piece + 1 >= 0 && piece + 2 < c->xg_T) pass = (c->aepre_layers - 3) * ipl_;
+  if (net == 0 && c->form.passengers && piece >= 0 && piece + 1 < c->xg_T) pass = c->aepre_layers * ipl_;
   // always 128 team workgroups (8 teams of 16, one team per XCD): more could starve the other stream of CUs while they poll for it
   if (c->trace_frame >= 0 && piece == c->trace_frame) hipLaunchKernelGGL(xgroup_kernel<true>, dim3(128 + pass), dim3(512), pass ? hsplit_smem(32) : 0, st, p);      // DCTTS_TRACE: stamped
   else hipLaunchKernelGGL(xgroup_kernel<false>, dim3(128 + pass), dim3(512), pass ? hsplit_smem(32) : 0, st, p);
@@ -715,26 +698,26 @@ static int v3_xgroup_launch(dctts_ctx* c, int B, int piece, int net, hipStream_t
 }
 
 // ---- xcone_kernel plumbing: one XConeParams per frame in device memory (layers HC_3 .. HC_7 of AudioDec's cone, parity copies folded in)
-static int v3_xcone_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool insig) {
-  const bool fold = c->side_fold && c->cone_len[0] - 1 <= 96 && c->cone_len[1] <= 96 && c->audiodec.size() > 1 && c->audiodec[1].wpp && c->audiodec[1].tap_off[1] == -1;
-  c->side_fold = fold;
-  const std::string g = geom("xc", B, T) + ":" + std::to_string((size_t)w.pb3[2]) + ":" + std::to_string((size_t)w.ad[1].p) + ":" + std::to_string((size_t)c->xg_mem) + ":" + std::to_string((int)insig) + ":" + std::to_string((size_t)c->wait_ctr) + ":" + std::to_string((int)c->tail_on) + ":" + std::to_string(c->np_eff) + ":" + std::to_string(c->trace_frame) +
-                        ":" + std::to_string((int)fold) + ":" + std::to_string((int)c->ae_pass) + ":" + std::to_string((size_t)w.kv.p) + ":" + std::to_string((size_t)w.vw) + ":" + std::to_string((size_t)w.pm_all) + ":" + std::to_string((size_t)w.scal.p);
+static int v3_xcone_table(dctts_ctx* c, const DecodeWs& w, int B, int T) {
+  const DecodeForm& fm = c->form;
+  const bool fold = fm.side_fold;
+  const std::string g = geom("xc", B, T) + ":" + fm.key() + ":" + std::to_string((size_t)w.pb3[2]) + ":" + std::to_string((size_t)w.ad[1].p) + ":" + std::to_string((size_t)c->xg_mem) + ":" + std::to_string((size_t)c->wait_ctr) + ":" + std::to_string(c->trace_frame) +
+                        ":" + std::to_string((size_t)w.kv.p) + ":" + std::to_string((size_t)w.vw) + ":" + std::to_string((size_t)w.pm_all) + ":" + std::to_string((size_t)w.scal.p);
   if (c->xc_tab && c->xc_geom == g) return 0;
   { dctts_ctx::TabSlot ts; if (tab_lookup(c, "xc", g, &ts)) { c->xc_tab = ts.tab; c->xc_geom = g; return 0; } }
   c->xc_tab = nullptr;
   const std::vector<DevLayer>& AD = c->audiodec;
   const XgMem m = xg_mem(c, B);
   size_t i0 = 2, i1 = i0; while (i1 < AD.size() && AD[i1].hc) ++i1;     // HC_3 .. the last highway layer
-  const int tail = c->tail_on ? 1 : 0;
-  if (tail) i1 = i0 + 2 + (size_t)(c->np_eff - 3);                       // HC_3, HC_4 (round 6: + HC_5) and the last one's cone rows: the chain's xtail_kernel takes it from there
+  const int tail = fm.xtail_on ? 1 : 0;
+  if (tail) i1 = i0 + 2 + (size_t)(fm.np - 3);                      // HC_3, HC_4 (round 6: + HC_5) and the last one's cone rows: the chain's xtail_kernel takes it from there
   const int L = (int)(i1 - i0);
   if (L < 1 || L > 5) return fail(DCTTS_ERR_STATE, "xcone: 1..5 highway layers behind HC_2");
   std::vector<XConeParams> tab((size_t)T);
   for (int f = 0; f < T; ++f) {
     const long par = f & 1;
     XConeParams p; memset(&p, 0, sizeof(p));
-    p.B = B; p.L = L; p.frame = f; p.tail_rows = tail; p.U = c->team_u;
+    p.B = B; p.L = L; p.frame = f; p.tail_rows = tail; p.U = fm.team_u;
     for (int k = 0; k < L; ++k) {
       const size_t i = i0 + k; const DevLayer& Ly = AD[i];
       if (Ly.cout != 256 || Ly.cin != 256 || Ly.cin_p != 256 || Ly.ntaps != 3 || Ly.tap_off[2] != 0 || !Ly.wp16 || c->cone_len[i] > 64) return fail(DCTTS_ERR_STATE, "xcone: causal k=3 highway layers over 256 channels, <= 64 cone rows");
@@ -747,10 +730,10 @@ static int v3_xcone_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool in
       q.offs = c->cone3_dev[i]; q.R = c->cone_len[i];
       for (int t3 = 0; t3 < 3; ++t3) q.tap_off[t3] = Ly.tap_off[t3];
     }
-    p.bar = m.bar_cone; p.bar_base = (unsigned)f * (unsigned)team_rounds(B, c->team_u) * (unsigned)(2 * L - 1 + tail + (fold ? 2 : 0)) * 16u; p.err = m.err;      // (utterance groups of a team in turn)
+    p.bar = m.bar_cone; p.bar_base = (unsigned)f * (unsigned)team_rounds(B, fm.team_u) * (unsigned)(2 * L - 1 + tail + (fold ? 2 : 0)) * 16u; p.err = m.err;      // (utterance groups of a team in turn)
     if (fold) { p.fold = 1; p.rc1 = fill_rowc1(c, w, B, c->cfg.max_N, f); p.rhc2 = fill_rowhc2(c, w, B, c->cfg.max_N, f); }
-    if (insig) {                                                // the launch's last team publishes "side-stream piece f complete" itself
-      p.done = (unsigned*)m.err + 1; p.done_target = (unsigned)(f + 1) * (unsigned)(((B + c->team_u - 1) / c->team_u < 8) ? (B + c->team_u - 1) / c->team_u : 8);      // one count per team (at most 8)
+    if (fm.side_signals_inkernel) {                             // the launch's last team publishes "side-stream piece f complete" itself
+      p.done = (unsigned*)m.err + 1; p.done_target = (unsigned)(f + 1) * (unsigned)(((B + fm.team_u - 1) / fm.team_u < 8) ? (B + fm.team_u - 1) / fm.team_u : 8);      // one count per team (at most 8)
       p.sig = c->wait_ctr + 32; p.sig_val = (unsigned)(f + 1);
       if (f + 1 < T) { p.wait = c->wait_ctr; p.wait_val = (unsigned)(f + 1); p.wait_err = (int*)(c->wait_ctr + 64); }      // what side-stream piece f + 1 starts from
     }
@@ -818,7 +801,7 @@ static int fill_xmlp(dctts_ctx* c, const DecodeWs& w, int B, int T, int j, size_
     x->wp = L.wp16; x->bias = L.bias; x->g = L.g1; x->be = L.b1; x->nkg = L.cin_p / 16; x->cout = L.cout; x->act = mel ? ACT_SIGMOID : L.act; x->pad_ = 0;
     return 0;
   };
-  const int rounds = team_rounds(B, c->team_u);
+  const int rounds = team_rounds(B, c->form.team_u);
   XMlpParams p; memset(&p, 0, sizeof(p));
   const long par = j & 1;
   p.B = B;
@@ -859,14 +842,15 @@ static int v3_xmlp_table(dctts_ctx* c, const DecodeWs& w, int B, int T) {
 }
 
 // xtail_kernel's per-frame parameters: AudioDec's last three highway layers (HC_5 .. HC_7 over 5 / 3 / 1 rows per utterance) + the k = 1 layers
-static int v3_xtail_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool insig, bool cwait) {
-  const std::string g = geom("xtail", B, T) + ":" + std::to_string((size_t)w.pd[0]) + ":" + std::to_string((size_t)w.ypad.p) + ":" + std::to_string((size_t)w.ad[0].p) + ":" + std::to_string((size_t)w.pe[0]) + ":" + std::to_string((size_t)c->xg_mem) + ":" + std::to_string(c->trace_frame) + ":" +
-                        std::to_string((int)c->dec_merge) + ":" + std::to_string(c->np_eff) + ":" + std::to_string((int)insig) + ":" + std::to_string((int)cwait) + ":" + std::to_string((size_t)c->sig_ptr) + ":" + std::to_string((size_t)c->wait_ctr) + ":" + std::to_string((size_t)c->aepre_tab) + ":" + std::to_string((int)c->ae_pass) + ":" + std::to_string((size_t)w.pb3[1]) + ":" + std::to_string((int)c->chain_one);
+static int v3_xtail_table(dctts_ctx* c, const DecodeWs& w, int B, int T) {
+  const DecodeForm& fm = c->form;
+  const std::string g = geom("xtail", B, T) + ":" + fm.key() + ":" + std::to_string((size_t)w.pd[0]) + ":" + std::to_string((size_t)w.ypad.p) + ":" + std::to_string((size_t)w.ad[0].p) + ":" + std::to_string((size_t)w.pe[0]) + ":" + std::to_string((size_t)c->xg_mem) + ":" + std::to_string(c->trace_frame) + ":" +
+                        std::to_string((size_t)c->sig_ptr) + ":" + std::to_string((size_t)c->wait_ctr) + ":" + std::to_string((size_t)c->aepre_tab) + ":" + std::to_string((size_t)w.pb3[1]);
   if (c->xtail_tab && c->xtail_geom == g) return 0;
   { dctts_ctx::TabSlot ts; if (tab_lookup(c, "xtail", g, &ts)) { c->xtail_tab = ts.tab; c->xtail_geom = g; return 0; } }
   c->xtail_tab = nullptr;
   const std::vector<DevLayer>& AD = c->audiodec;                         // (the full layers: all three taps in wp16)
-  const int NPv = c->dec_merge ? c->np_eff : 3, NHv = 6 - NPv;           // newest-row layers in front / cone layers behind them (xtail_kernel.h: NP)
+  const int NPv = fm.np, NHv = 6 - NPv;          // newest-row layers in front / cone layers behind them (xtail_kernel.h: NP)
   const size_t h0 = (size_t)(1 + NPv);                                   // NP = 3: C_1, HC_2, HC_3, HC_4 | HC_5, HC_6, HC_7 | C_8 ..;  NP = 4: ... HC_5 | HC_6, HC_7 | C_8 ..
   for (size_t k = 0; k < (size_t)NHv; ++k) {
     const DevLayer& Ly = AD[h0 + k];
@@ -884,10 +868,10 @@ static int v3_xtail_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool in
   std::vector<XTailParams> tab((size_t)T);
   for (int j = 0; j < T; ++j) {
     XTailParams p; memset(&p, 0, sizeof(p));
-    CHK(fill_xmlp(c, w, B, T, j, h0 - 1, m, c->dec_merge ? (c->chain_one ? 14 : 13) : 10, &p.m));      // (chain_one: + the meeting in front of the AudioEnc run, xchain_kernel)
+    CHK(fill_xmlp(c, w, B, T, j, h0 - 1, m, fm.dec_merged ? (fm.one_launch ? 14 : 13) : 10, &p.m));      // (one_launch: + the meeting in front of the AudioEnc run, xchain_kernel)
     p.m.xch_set = m.bpad * 512; p.m.sch_set = m.bpad * 64;      // (value, tag) pairs
     const long par = j & 1;
-    if (c->dec_merge) {
+    if (fm.dec_merged) {
       // merged form: AudioDec HC_2 .. HC_4 at the newest row run in front (what the AudioDec run of xgroup_kernel did, v3_xgroup_table), and this launch is the
       // first one of chain piece j: it publishes the chain's counter, waits for side-stream piece j, and carries the passengers
       const std::vector<DevLayer>& ADc = c->ad_c;                         // (centre tap in wp16)
@@ -901,19 +885,19 @@ static int v3_xtail_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool in
         q.presum = w.pb3[i] + par * w.pb3_set[i] + (long)(c->cone_len[i] - 1) * 512; q.presum_bs = c->cone_len[i] * 512;
       }
       p.xchp = m.xch[0]; p.schp = m.sch[0]; p.xchp_set = m.bpad * 512; p.schp_set = m.bpad * 64;
-      if (insig) { p.sig = c->sig_ptr; p.sig_val = (unsigned)(j + 1); }
-      if (cwait) { p.wait2 = c->wait_ctr + 32; p.wait_val = (unsigned)(j + 1); }
-      if (c->ae_pass && j + 1 < T) {                                      // passengers: AudioEnc's presums of row j + 1 and row j of the C1Q . W2 cache (counted: rowc1_kernel polls psig)
+      if (fm.chain_signals_inkernel) { p.sig = c->sig_ptr; p.sig_val = (unsigned)(j + 1); }
+      if (fm.chain_waits_inkernel) { p.wait2 = c->wait_ctr + 32; p.wait_val = (unsigned)(j + 1); }
+      if (fm.passengers && j + 1 < T) {                                   // passengers: AudioEnc's presums of row j + 1 and row j of the C1Q . W2 cache (counted: rowc1_kernel polls psig)
         const int ipl = ((B + 31) / 32) * (c->cfg.d / 32);
-        // chain_one: the AudioEnc run that reads the presums is part of THIS launch, and passengers run on other XCDs: they compute row j + 2's (inputs: rows <= j,
+        // one_launch: the AudioEnc run that reads the presums is part of THIS launch, and passengers run on other XCDs: they compute row j + 2's (inputs: rows <= j,
         // complete since the previous piece) for the next launch; the C1Q . W2 descriptors carry step_val 0 then, so their row stays j
-        const int ps = c->chain_one ? j + 2 : j + 1;
+        const int ps = fm.one_launch ? j + 2 : j + 1;
         p.ptab = (const SplitParams*)c->aepre_tab + (size_t)(ps & 1) * aepre_stride(c);
         p.p_ipl = ipl; p.p_blocks = c->aepre_layers * ipl; p.p_step = ps; p.p_count_from = c->aepre_layers - 3;
         p.pdone = (unsigned*)m.err + 2; p.pdone_target = (unsigned)(j + 1) * (unsigned)(3 * ipl); p.psig = c->wait_ctr + 16; p.psig_val = (unsigned)(j + 1);
       }
     }
-    p.nh = NHv; p.nin0 = nin0; p.frame = j; p.U = c->team_u;
+    p.nh = NHv; p.nin0 = nin0; p.frame = j; p.U = fm.team_u;
     for (int k = 0; k < NHv; ++k) {
       const DevLayer& Ly = AD[h0 + k];
       XTailHc& q = p.hc[k];
@@ -951,22 +935,22 @@ static int v3_xtail_table(dctts_ctx* c, const DecodeWs& w, int B, int T, bool in
 
 static int v3_mlp_launch(dctts_ctx* c, int B, int j, hipStream_t st) {
   CHK(prof_close_run(c, st));
-  if (c->tail_on && c->xtail_tab) {
+  if (c->form.xtail_on && c->xtail_tab) {
     const bool prof = c->prof_id == DCTTS_PROF_XTAIL && c->prof_frame;      // measurement (dctts_hip_debug.h): HIP events around the launch of every 16th frame
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (prof) { HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1)); HIPCHK(hipEventRecord(e0, st)); }
     int pass = 0;                                                 // passenger workgroups, as in the table
-    if (c->dec_merge && c->ae_pass && j + 1 < c->xg_T) pass = c->aepre_layers * (((B + 31) / 32) * (c->cfg.d / 32));
-    if (c->chain_one && j + 1 < c->xg_T) {
+    if (c->form.dec_merged && c->form.passengers && j + 1 < c->xg_T) pass = c->aepre_layers * (((B + 31) / 32) * (c->cfg.d / 32));
+    if (c->form.one_launch && j + 1 < c->xg_T) {
       // round 5: the whole chain piece as ONE launch -- these layers, a team barrier, the AudioEnc run of frame j + 1 with the attention row and AudioDec C_1
       const XGroupParams* pg = (const XGroupParams*)c->xg_tab + (size_t)2 * (j + 1) + 1;
       const XTailParams* pt = (const XTailParams*)c->xtail_tab + j;
-      if (c->np_eff == 4) {
+      if (c->form.np == 4) {
         if (c->trace_on) hipLaunchKernelGGL((xchain_kernel<true, 4>), dim3(128 + pass), dim3(512), 0, st, pt, pg);
         else hipLaunchKernelGGL((xchain_kernel<false, 4>), dim3(128 + pass), dim3(512), 0, st, pt, pg);
       } else if (c->trace_on) hipLaunchKernelGGL((xchain_kernel<true, 3>), dim3(128 + pass), dim3(512), 0, st, pt, pg);
       else hipLaunchKernelGGL((xchain_kernel<false, 3>), dim3(128 + pass), dim3(512), 0, st, pt, pg);
-    } else if (c->dec_merge && c->np_eff == 4) {
+    } else if (c->form.np == 4) {
       if (c->trace_on) hipLaunchKernelGGL((xtail_kernel<true, 4>), dim3(128 + pass), dim3(512), 0, st, (const XTailParams*)c->xtail_tab + j);
       else hipLaunchKernelGGL((xtail_kernel<false, 4>), dim3(128 + pass), dim3(512), 0, st, (const XTailParams*)c->xtail_tab + j);
     } else if (c->trace_on) hipLaunchKernelGGL((xtail_kernel<true, 3>), dim3(128 + pass), dim3(512), 0, st, (const XTailParams*)c->xtail_tab + j);      // DCTTS_TRACE: stamped instantiation
@@ -975,7 +959,7 @@ static int v3_mlp_launch(dctts_ctx* c, int B, int j, hipStream_t st) {
     if (prof) { HIPCHK(hipEventRecord(e1, st)); c->prof_ev.emplace_back(e0, e1); c->prof_cnt.push_back(1); c->prof_rows += 10; }
     return 0;
   }
-  if (c->xmlp_on && c->xmlp_tab) {
+  if (c->form.xmlp_on && c->xmlp_tab) {
     hipLaunchKernelGGL(xmlp_kernel, dim3(128), dim3(512), 0, st, (const XMlpParams*)c->xmlp_tab + j);
     HIPCHK(hipGetLastError());
     return 0;
@@ -994,9 +978,9 @@ static int v3_mlp_launch(dctts_ctx* c, int B, int j, hipStream_t st) {
 static int v3_chain_dec(dctts_ctx* c, const DecodeWs& w, int B, int j, hipStream_t sm) {
   const std::vector<DevLayer>& AD = c->ad_c;
   const int par = j & 1;
-  if (c->xg_on) {                                               // the newest-row layers as one launch (its table entry carries the piece's signal / wait) ...
+  if (c->form.xgroup_on) {                                               // the newest-row layers as one launch (its table entry carries the piece's signal / wait) ...
     c->sig_next = 0; c->wait2_next = 0;
-    if (c->dec_merge) return 0;                                 // ... or as the front of xtail_kernel's launch (v3_mlp_launch, called next)
+    if (c->form.dec_merged) return 0;                                 // ... or as the front of xtail_kernel's launch (v3_mlp_launch, called next)
     return v3_xgroup_launch(c, B, j, 0, sm);
   }
   for (size_t i = 1; i < AD.size(); ++i) {
@@ -1018,8 +1002,8 @@ static int v3_chain_enc(dctts_ctx* c, const DecodeWs& w, int B, int N, int j, hi
     if (j > 0 && !AE[i].hc) continue;                           // C_1 .. C_3 of frame j ran inside frame j-1's mlp_rows_kernel
     if (i == 0) {                                               // frame 0 only: S[0] is the zero row
       CHK(run_split(c, 16, AE[0], B, 1, nullptr, j, PRO_RAW, nullptr, nullptr, w.ypad, w.pe[0], sm, nullptr, w.se[0]));
-    } else if (c->xg_on && AE[i].hc) {
-      if (!AE[i - 1].hc && !(c->chain_one && j >= 1)) CHK(v3_xgroup_launch(c, B, j - 1, 1, sm));    // the whole run of highway layers (HC_4 .. HC_13) of frame j, launched from chain piece j - 1
+    } else if (c->form.xgroup_on && AE[i].hc) {
+      if (!AE[i - 1].hc && !(c->form.one_launch && j >= 1)) CHK(v3_xgroup_launch(c, B, j - 1, 1, sm));    // the whole run of highway layers (HC_4 .. HC_13) of frame j, launched from chain piece j - 1
                                                                                                      // (chain_one: it ran as the back of that piece's one launch, v3_mlp_launch)
     } else {
       SplitExtra ex;
@@ -1028,7 +1012,7 @@ static int v3_chain_enc(dctts_ctx* c, const DecodeWs& w, int B, int N, int j, hi
                      w.pe[i], w.se[i], &ex, sm));
     }
   }
-  if (c->attn_fold) return 0;                                   // the AudioEnc run's launch carried the attention row and AudioDec C_1 (xgroup_kernel.h)
+  if (c->form.attn_fold) return 0;                                   // the AudioEnc run's launch carried the attention row and AudioDec C_1 (xgroup_kernel.h)
   const size_t la = AE.size() - 1;
   AttnQParams a; memset(&a, 0, sizeof(a));
   a.B = B; a.frame = j;
@@ -1082,13 +1066,13 @@ static int write_trace3(dctts_ctx* c, int j) {
     for (int i = 2; i < 120 && o[i]; ++i) fprintf(f, " %6.2f%s", (o[i] - o[0]) / 100.0, ((i - 2) % 5 == 4) ? " |" : "");
     fprintf(f, "\n");
     const long long* ot = &h[64 * 64 * 32 - 64];
-    if (net && c->chain_one && ot[0]) fprintf(f, "  (one launch per chain piece: this run was entered %.2f us after xtail_kernel's part of the launch below was)\n", (o[0] - ot[0]) / 100.0);
+    if (net && c->form.one_launch && ot[0]) fprintf(f, "  (one launch per chain piece: this run was entered %.2f us after xtail_kernel's part of the launch below was)\n", (o[0] - ot[0]) / 100.0);
   }
   {
     const long long* o = &h[64 * 64 * 32 - 192];
     if (o[0]) {
       fprintf(f, "# xcone_kernel (workgroup 0, thread 0), microseconds since its entry%s; per layer: row tables | contraction done | barrier passed | row pass done | barrier passed\n ",
-              c->side_fold ? "; folded form: C_1's cone rows done | barrier passed | HC_2's cone rows done | barrier passed, then" : "");
+              c->form.side_fold ? "; folded form: C_1's cone rows done | barrier passed | HC_2's cone rows done | barrier passed, then" : "");
       int last = 0;
       for (int i = 1; i < 60 && o[i]; ++i) { fprintf(f, " %6.2f", (o[i] - o[0]) / 100.0); last = i; }
       if (last > 0 && o[101] > o[100]) fprintf(f, "   (shader clock over the launch: %.0f MHz)", (double)(o[101] - o[100]) / ((o[last] - o[0]) / 100.0));
@@ -1099,15 +1083,15 @@ static int write_trace3(dctts_ctx* c, int j) {
         fprintf(f, "\n");
       }
       const long long* ot = &h[64 * 64 * 32 - 64];          // the chain launch of the same frame (the stamps are one wall clock): when did this side piece run relative to it?
-      if (ot[0] && c->tail_on && last > 0) fprintf(f, "  (relative to the entry of the chain's launch of this frame: entered %.2f, last stamp %.2f us)\n", (o[0] - ot[0]) / 100.0, (o[last] - ot[0]) / 100.0);
+      if (ot[0] && c->form.xtail_on && last > 0) fprintf(f, "  (relative to the entry of the chain's launch of this frame: entered %.2f, last stamp %.2f us)\n", (o[0] - ot[0]) / 100.0, (o[last] - ot[0]) / 100.0);
     }
   }
   {
     const long long* o = &h[64 * 64 * 32 - 64];
-    if (o[0] && c->tail_on) {
+    if (o[0] && c->form.xtail_on) {
       int i0 = 2;
-      if (c->dec_merge) {
-        const int npv = c->np_eff;
+      if (c->form.dec_merged) {
+        const int npv = c->form.np;
         fprintf(f, "# xtail_kernel, merged form (workgroup 0, thread 0), microseconds since its entry: first row built (incl. the wait for the side stream) | end of each newest-row layer (HC_2 .. HC_%d) | cone rows in LDS | per cone layer (HC_%d .. HC_7): MFMAs issued + partial sums written, reduced + published, barrier passed, exchanged rows landed, rows rebuilt | then the end of every k = 1 layer\n ", npv + 1, npv + 2);
         fprintf(f, " %6.2f |", (o[1] - o[0]) / 100.0);
         for (int i = 2; i < 2 + npv && o[i]; ++i) fprintf(f, " %6.2f", (o[i] - o[0]) / 100.0);
@@ -1117,7 +1101,7 @@ static int write_trace3(dctts_ctx* c, int j) {
         fprintf(f, "# xtail_kernel (workgroup 0, thread 0), microseconds since its entry: rows staged + newest row rebuilt | per highway layer: MFMAs issued + partial sums written, reduced + published, barrier passed, exchanged rows landed, rows rebuilt | then the end of every k = 1 layer\n ");
         fprintf(f, " %6.2f |", (o[1] - o[0]) / 100.0);
       }
-      const int ncone = c->dec_merge ? 5 * (6 - c->np_eff) : 15;
+      const int ncone = 5 * (6 - c->form.np);
       for (int i = i0; i < 56 && o[i]; ++i) fprintf(f, " %6.2f%s", (o[i] - o[0]) / 100.0, (i < i0 + ncone && (i - i0) % 5 == 4) ? " |" : "");
       if (o[56] && o[58]) fprintf(f, "\n  passengers: the first one ran %.2f .. %.2f, the last one %.2f .. %.2f", (o[56] - o[0]) / 100.0, (o[57] - o[0]) / 100.0, (o[58] - o[0]) / 100.0, (o[59] - o[0]) / 100.0);
       fprintf(f, "\n");
@@ -1132,69 +1116,53 @@ static int write_trace3(dctts_ctx* c, int j) {
   return 0;
 }
 
-static int decode_v3(dctts_ctx* c, const DecodeWs& w, int B, int N, int T, hipStream_t st) {
+// What the loaded networks and this context allow (decode_form.h): the persistent part (c->caps) + the running timing id + the geometry predicates
+static DecodeCaps decode_caps(const dctts_ctx* c) {
+  DecodeCaps cap = c->caps;
+  const std::vector<DevLayer>& AD = c->audiodec;
+  cap.prof_id = c->prof_id;
+  cap.std_cone_tail = AD.size() == 11 && c->cone_len.size() > 6 && c->cone_len[4] == 5 && c->cone_len[5] == 3 && c->cone_len[6] == 1;
+  cap.hc2_presum = AD.size() > 1 && AD[1].wpp && AD[1].tap_off[1] == -1;
+  cap.c1q_wp16 = c->ad_c1q.wp16 != nullptr;
+  cap.d256 = c->cfg.d == 256;
+  cap.c1_has_cone = c->cone_len[0] > 1;
+  cap.side_fold_rows_ok = c->cone_len[0] - 1 <= 96 && c->cone_len.size() > 1 && c->cone_len[1] <= 96;
+  return cap;
+}
+
+static int decode_v3(dctts_ctx* c, const DecodeKnobs& knobs, const DecodeWs& w, int B, int N, int T, hipStream_t st) {
+  c->form = resolve_decode_form(knobs, decode_caps(c), B);      // the one place the form is decided; everything below reads it
+  const DecodeForm& fm = c->form;
   CHK(decode_streams_init(c));
   // How the two streams meet (DESIGN.md sections 2b / 2c).  Default (chain_wait_inkernel): two counters in device memory that kernels poll and
   // write themselves -- the chain's is written by the first launch of the NEXT chain piece and polled by xcone_kernel's tail, the side stream's
   // is written by xcone_kernel's last team and polled by the chain piece's first launch; no stream operation per frame.  DCTTS_CHAIN_WAIT=0:
   // the same counters as stream memory operations (hipStreamWriteValue32 / hipStreamWaitValue32) around the pieces.
   // Fallback (no stream memory operations on the device, or DCTTS_SYNC_VALUES=0, which rocprofv3 --pmc needs): events.
-  if (c->sync_values && !c->ctr_chain) {
-    int can = 0; (void)hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device);
-    if (!can) c->sync_values = 0;
-  }
-  const bool vs = c->sync_values != 0;
-  if (vs && !c->ctr_chain) {
+  // With in-kernel waits and xcone_kernel both meetings of a frame leave the command processor, and the small presum GEMMs need no launch of their own: AudioEnc's
+  // presums and the newest row of the C1Q . W2 cache are passengers of the chain's first launch (DecodeForm::passengers; rowc1 polls the row's own counter).
+  if (fm.counters && !c->ctr_chain) {
     // Stream memory operations: a write packet after a piece, a compare-and-wait packet before the piece that needs it.  The
     // command processor polls the counter itself: no signal objects, no interrupt, and (measured) ~10 us less per frame on the
     // chain's stream than hipEventRecord + hipStreamWaitEvent.
     HIPCHK(hipExtMallocWithFlags((void**)&c->ctr_chain, 8, hipMallocSignalMemory));
     HIPCHK(hipExtMallocWithFlags((void**)&c->ctr_bulk, 8, hipMallocSignalMemory));
   }
-  const bool insig = vs;                                    // the chain's counter is written by the first launch of the next piece
-  const bool cwait = vs && c->chain_wait_inkernel;          // the chain's wait for the bulk's counter happens inside that launch (chain3_kernel: wait2)
-  if (cwait && !c->wait_ctr) {
+  if (fm.chain_waits_inkernel && !c->wait_ctr) {
     HIPCHK(hipMalloc((void**)&c->wait_ctr, 128 * sizeof(unsigned)));
     HIPCHK(dev_zero_now(c->wait_ctr, 128 * sizeof(unsigned)));
   }
   CHK(v3_mlp_table(c, w, B, T));
-  c->xg_on = c->xgroup != 0 && c->xgroup_ok && c->prof_id != DCTTS_PROF_CHAIN_HC;      // (that timing id looks at chain3_kernel launches; so does DCTTS_TRACE with DCTTS_XGROUP=0)
-  c->xc_on = c->xcone != 0 && c->xgroup_ok && c->prof_id != DCTTS_PROF_BULK_GEMM &&
-             c->audiodec.size() > 1 && c->audiodec[1].wpp && c->audiodec[1].tap_off[1] == -1;      // (behind rowhc2_kernel)
-  c->tail_on = c->xg_on && c->xc_on && c->chain_tail >= 2 && c->audiodec.size() == 11 && c->cone_len.size() > 6 && c->cone_len[4] == 5 && c->cone_len[5] == 3 && c->cone_len[6] == 1;
-  c->xmlp_on = c->xg_on && c->chain_tail >= 1 && !c->tail_on;
-  c->dec_merge = c->tail_on && (c->chain_tail == 2 || c->chain_tail == 6);          // (5: xtail_kernel behind an AudioDec run of xgroup_kernel, the first round-4 form -- A/B)
-  c->np_eff = (c->dec_merge && c->tail_np == 4) ? 4 : 3;
-  c->team_u = team_u_for(c, B);
-  c->attn_fold = c->xg_on && c->chain_tail >= 1 && c->chain_tail != 3 && c->cfg.d == 256 && c->ad_c1q.wp16 != nullptr;      // (3: xtail_kernel without the fold -- A/B)
-  c->chain_one = c->dec_merge && c->chain_tail == 2 && c->attn_fold;      // (6: the chain piece as two launches, round 4's form -- A/B)
-  // with in-kernel waits both stream meetings of a frame leave the command processor: the side stream's first launch polls the chain's
-  // counter, and xcone_kernel's last team writes the side stream's
-  const bool bsig = cwait && c->xc_on;
-  // ... and the one small GEMM in front of the cone work (the newest row of the C1Q . W2 cache) rides in the chain's AudioEnc presum launch one piece
-  // earlier: its input is the chain's own newest row, and the counter the side stream waits for is written by the launch behind it
-  // (round 4, measured and switched off: the presum GEMMs as launches of their own on the SIDE stream -- the newest C1Q . W2 row in front of the row kernels,
-  //  AudioEnc's presums between rowhc2_kernel and xcone_kernel -- instead of as passenger workgroups of the chain's AudioDec launch, where they only find CUs
-  //  once that launch's teams have finished (~4 us): the two hbulk_group_kernel launches take 11 + 10.7 us on the side stream, which then bounds the frame at
-  //  99.5 us against 89.3)
-  c->side_pre = false;
-  c->side_fold = c->xcone == 1 && c->xc_on && bsig;      // (needs the team kernels and their in-kernel stream meetings; v3_xcone_table checks the cone geometry)
-  c->c1qw_chain = vs && c->xc_on && !c->side_pre;
-  // ... or, with both team kernels, in no launch of its own at all: the AudioEnc presums and that row are passengers of the chain's AudioDec launch
-  // (xgroup_kernel.h); the side stream's first launch (rowc1_kernel) polls the row's own counter before it ends
-  c->ae_pass = bsig && c->xg_on && c->cone_len[0] > 1 && !c->side_pre;
-  c->chain_one = c->chain_one && c->ae_pass;
-  c->ae_pass_split = c->ae_pass && c->chain_tail == 4;      // (4: A/B -- measured: the AudioDec launch gets 3.4 us shorter, the AudioEnc launch 6 us longer: its passengers only find CUs when xcone_kernel's work ends, ~4 us before the launch's own teams do: 88.9 against 86.2 us per frame)
-  CHK(v3_aepre_table(c, w, B, c->c1qw_chain));
-  c->sig_ptr = cwait ? c->wait_ctr : (unsigned*)c->ctr_chain;
-  if (c->xg_on || c->xc_on) {
-    CHK(v3_xgroup_table(c, w, B, T, insig, cwait));            // (also allocates the memory both kernels meet through)
-    if (c->xc_on) CHK(v3_xcone_table(c, w, B, T, bsig));
+  CHK(v3_aepre_table(c, w, B));
+  c->sig_ptr = fm.chain_waits_inkernel ? c->wait_ctr : (unsigned*)c->ctr_chain;
+  if (fm.xgroup_on || fm.xcone_on) {
+    CHK(v3_xgroup_table(c, w, B, T));                          // (also allocates the memory both kernels meet through)
+    if (fm.xcone_on) CHK(v3_xcone_table(c, w, B, T));
     const XgMem m = xg_mem(c, B);
     HIPCHK(hipMemsetAsync(m.bar, 0, (3 * m.bar_words + 64) * sizeof(unsigned), st));      // the three sets of team barriers and the error word
-    if (c->xmlp_on) CHK(v3_xmlp_table(c, w, B, T));
-    if (c->tail_on) {
-      CHK(v3_xtail_table(c, w, B, T, insig, cwait));
+    if (fm.xmlp_on) CHK(v3_xmlp_table(c, w, B, T));
+    if (fm.xtail_on) {
+      CHK(v3_xtail_table(c, w, B, T));
       HIPCHK(hipMemsetAsync(m.xch_m, 0, (size_t)(2 * m.bpad * 512 + 2 * m.bpad * 64) * sizeof(float), st));      // the tagged exchange: a tag of the previous decode must not look current
     }
   }
@@ -1203,17 +1171,17 @@ static int decode_v3(dctts_ctx* c, const DecodeWs& w, int B, int N, int T, hipSt
   // launch per chain piece costs ~10 us of start-up on the critical path)
   const bool gr = c->use_graph != 0;
   auto chain_piece = [&](int j, hipStream_t s) -> int {      // j = -1: AudioEnc / attention / AudioDec C_1 of frame 0 only
-    c->sig_next = (insig && j >= 0) ? (unsigned)(j + 1) : 0u;          // written by the piece's first launch (AudioDec HC_2)
-    c->wait2_next = (cwait && j >= 0) ? (unsigned)(j + 1) : 0u;        // ... which also waits for bulk piece j
+    c->sig_next = (fm.chain_signals_inkernel && j >= 0) ? (unsigned)(j + 1) : 0u;          // written by the piece's first launch (AudioDec HC_2)
+    c->wait2_next = (fm.chain_waits_inkernel && j >= 0) ? (unsigned)(j + 1) : 0u;        // ... which also waits for bulk piece j
     // AudioEnc's presums of row j+1 (inputs: rows <= j-1, final since piece j-2): when the side stream is the longer one they run here, while this
     // piece would otherwise wait for it, instead of in front of the cone work
-    if (j >= 0 && c->xc_on && !c->ae_pass && !c->side_pre && j + 1 < T) CHK(v3_aepre(c, B, j + 1, s, c->c1qw_chain ? 0 : 1));
+    if (j >= 0 && fm.xcone_on && !fm.passengers && j + 1 < T) CHK(v3_aepre(c, B, j + 1, s, fm.c1qw_on_chain ? 0 : 1));
     if (j >= 0) { CHK(v3_chain_dec(c, w, B, j, s)); CHK(v3_mlp_launch(c, B, j, s)); }   // AudioDec HC_2 .. HC_7; C_8 .. C_11, mel frame j, AudioEnc C_1 .. C_3 of frame j+1
     if (j + 1 < T) return v3_chain_enc(c, w, B, N, j + 1, s);
     return 0;
   };
   if (gr) {
-    const std::string g = geom("graph3", B, T, N) + ":" + std::to_string(c->bulk_cap) + ":" + std::to_string((size_t)c->mlp_tab) + ":" + std::to_string((int)cwait) + ":" + std::to_string((int)vs) + ":" + std::to_string((int)c->xg_on) + ":" + std::to_string((int)c->xc_on) + ":" + std::to_string((int)c->ae_pass) + ":" + std::to_string((int)c->side_pre) + ":" + std::to_string((size_t)c->xc_tab) + ":" + std::to_string((size_t)c->wait_ctr) + ":" +
+    const std::string g = geom("graph3", B, T, N) + ":" + std::to_string(c->bulk_cap) + ":" + std::to_string((size_t)c->mlp_tab) + ":" + fm.key() + ":" + std::to_string((size_t)c->xc_tab) + ":" + std::to_string((size_t)c->wait_ctr) + ":" +
                           std::to_string((size_t)w.kv.p) + ":" + std::to_string((size_t)w.vw);
     if (c->bulk3_g.empty() || c->graphs3_geom != g) {
       if (!c->bulk3_g.empty()) HIPCHK(hipDeviceSynchronize());      // (an earlier decode's graphs may still be running on another stream)
@@ -1223,28 +1191,28 @@ static int decode_v3(dctts_ctx* c, const DecodeWs& w, int B, int N, int T, hipSt
       const int prof_keep = c->prof_id; c->prof_id = -1;
       c->bulk3_g.assign(T, nullptr);
       int rc = 0;
-      for (int f = 0; f < T && rc == 0; ++f) rc = capture_piece(cs, &c->bulk3_g[f], [&]() { return v3_bulk_rest(c, w, B, N, T, f, cs, (cwait && f > 0) ? (unsigned)f : 0u); });
+      for (int f = 0; f < T && rc == 0; ++f) rc = capture_piece(cs, &c->bulk3_g[f], [&]() { return v3_bulk_rest(c, w, B, N, T, f, cs, (fm.chain_waits_inkernel && f > 0) ? (unsigned)f : 0u); });
       c->prof_id = prof_keep;
       HIPCHK(hipStreamDestroy(cs));
       if (rc != 0) { destroy_graphs(c); return rc; }
       c->graphs3_geom = g;
     }
   }
-  if (cwait) HIPCHK(hipMemsetAsync(c->wait_ctr, 0, 65 * sizeof(unsigned), st));      // the counters and THIS decode's wait error word ([64]; the sticky copy lives in dstat); st is ordered after the previous decode's last piece (and its decode_finish), and that piece after all bulk work
-  if (vs) {
+  if (fm.chain_waits_inkernel) HIPCHK(hipMemsetAsync(c->wait_ctr, 0, 65 * sizeof(unsigned), st));      // the counters and THIS decode's wait error word ([64]; the sticky copy lives in dstat); st is ordered after the previous decode's last piece (and its decode_finish), and that piece after all bulk work
+  if (fm.counters) {
     HIPCHK(hipStreamWriteValue32(st, c->ctr_chain, 0u, 0));
     HIPCHK(hipStreamWriteValue32(st, c->ctr_bulk, 0u, 0));
   }
   CHK(v3_vw(c, w, B, N, st));                                              // V . W_top, once per batch
   CHK(v3_aepre(c, B, 0, st));                                              // row 0's AudioEnc presums (= the biases: every tap reads padding)
-  if (c->chain_one && T > 1) CHK(v3_aepre(c, B, 1, st, 1));                // ... and row 1's (the same): piece j's passengers compute row j + 2's in this form
+  if (fm.one_launch && T > 1) CHK(v3_aepre(c, B, 1, st, 1));                // ... and row 1's (the same): piece j's passengers compute row j + 2's in this form
   HIPCHK(hipEventRecord(c->ev_fork, st));
   HIPCHK(hipStreamWaitEvent(sb, c->ev_fork, 0));
   const int tstep = c->trace_frame;
   auto bulk_piece = [&](int f) -> int {
-    if (gr) HIPCHK(hipGraphLaunch(c->bulk3_g[f], sb)); else CHK(v3_bulk_rest(c, w, B, N, T, f, sb, (cwait && f > 0) ? (unsigned)f : 0u));
-    if (bsig) return 0;
-    if (vs) HIPCHK(hipStreamWriteValue32(sb, cwait ? (void*)(c->wait_ctr + 32) : (void*)c->ctr_bulk, (uint32_t)(f + 1), 0)); else HIPCHK(hipEventRecord(c->ev_bulk[f & 3], sb));
+    if (gr) HIPCHK(hipGraphLaunch(c->bulk3_g[f], sb)); else CHK(v3_bulk_rest(c, w, B, N, T, f, sb, (fm.chain_waits_inkernel && f > 0) ? (unsigned)f : 0u));
+    if (fm.side_signals_inkernel) return 0;
+    if (fm.counters) HIPCHK(hipStreamWriteValue32(sb, fm.chain_waits_inkernel ? (void*)(c->wait_ctr + 32) : (void*)c->ctr_bulk, (uint32_t)(f + 1), 0)); else HIPCHK(hipEventRecord(c->ev_bulk[f & 3], sb));
     return 0;
   };
   // DCTTS_PIECETIME=<frame>: timing events around 8 consecutive chain / bulk pieces starting there (measurement only)
@@ -1254,16 +1222,16 @@ static int decode_v3(dctts_ctx* c, const DecodeWs& w, int B, int N, int T, hipSt
   auto ptime = [&](int j) { return pt0 >= 0 && j >= pt0 && j < pt0 + 8; };
   CHK(bulk_piece(0));
   CHK(chain_piece(-1, st));
-  if (!vs) HIPCHK(hipEventRecord(c->ev_chain[3], st));
+  if (!fm.counters) HIPCHK(hipEventRecord(c->ev_chain[3], st));
   for (int j = 0; j < T; ++j) {
     if (j + 1 < T) {
       // bulk piece j+1 needs attnq(j) / C1Q[j]: end of chain piece j-1
-      if (cwait) {} else if (vs) HIPCHK(hipStreamWaitValue32(sb, c->ctr_chain, (uint32_t)(j + 1), hipStreamWaitValueGte, 0xFFFFFFFFu)); else HIPCHK(hipStreamWaitEvent(sb, c->ev_chain[(j - 1) & 3], 0));
+      if (fm.chain_waits_inkernel) {} else if (fm.counters) HIPCHK(hipStreamWaitValue32(sb, c->ctr_chain, (uint32_t)(j + 1), hipStreamWaitValueGte, 0xFFFFFFFFu)); else HIPCHK(hipStreamWaitEvent(sb, c->ev_chain[(j - 1) & 3], 0));
       if (ptime(j + 1)) HIPCHK(hipEventRecord(pe_b[j + 1 - pt0][0], sb));
       CHK(bulk_piece(j + 1));
       if (ptime(j + 1)) HIPCHK(hipEventRecord(pe_b[j + 1 - pt0][1], sb));
     }
-    if (!cwait) { if (vs) HIPCHK(hipStreamWaitValue32(st, c->ctr_bulk, (uint32_t)(j + 1), hipStreamWaitValueGte, 0xFFFFFFFFu)); else HIPCHK(hipStreamWaitEvent(st, c->ev_bulk[j & 3], 0)); }
+    if (!fm.chain_waits_inkernel) { if (fm.counters) HIPCHK(hipStreamWaitValue32(st, c->ctr_bulk, (uint32_t)(j + 1), hipStreamWaitValueGte, 0xFFFFFFFFu)); else HIPCHK(hipStreamWaitEvent(st, c->ev_bulk[j & 3], 0)); }
     if (ptime(j)) HIPCHK(hipEventRecord(pe_c[j - pt0][0], st));
     if (j == tstep) {
       if (!c->trace_buf) { HIPCHK(hipMalloc((void**)&c->trace_buf, 64 * 64 * 32 * sizeof(long long))); }
@@ -1276,7 +1244,7 @@ static int decode_v3(dctts_ctx* c, const DecodeWs& w, int B, int N, int T, hipSt
     CHK(prof_close_run(c, st));
     c->prof_frame = false;
     if (ptime(j)) HIPCHK(hipEventRecord(pe_c[j - pt0][1], st));
-    if (!vs) HIPCHK(hipEventRecord(c->ev_chain[j & 3], st));
+    if (!fm.counters) HIPCHK(hipEventRecord(c->ev_chain[j & 3], st));
     if (c->trace_on) {
       c->trace_on = false;
       HIPCHK(hipStreamSynchronize(st));
@@ -1284,8 +1252,8 @@ static int decode_v3(dctts_ctx* c, const DecodeWs& w, int B, int N, int T, hipSt
     }
   }
   // the chain's last piece is on `st`; the bulk stream's last piece was consumed by it, so `st` is ordered after all decode work.
-  c->fin_xerr = (c->xg_on || c->xc_on) ? xg_mem(c, B).err : nullptr;      // this decode's error words, folded into the sticky status by decode_finish
-  c->fin_werr = cwait ? (const int*)(c->wait_ctr + 64) : nullptr;
+  c->fin_xerr = (fm.xgroup_on || fm.xcone_on) ? xg_mem(c, B).err : nullptr;      // this decode's error words, folded into the sticky status by decode_finish
+  c->fin_werr = fm.chain_waits_inkernel ? (const int*)(c->wait_ctr + 64) : nullptr;
   if (pt0 >= 0) {
     const int npt = T - pt0 < 8 ? T - pt0 : 8;      // frames of the window this decode ran (a decode shorter than the window reports the ones it has)
     if (npt > 0) { HIPCHK(hipStreamSynchronize(st)); HIPCHK(hipStreamSynchronize(sb)); }
@@ -1334,7 +1302,7 @@ static int decode_impl(dctts_ctx* c, const int32_t* L, int B, int N, int T, floa
     const int ew = c->dstat_host[0];
     c->dstat_host[0] = 0; c->dstat_host[1] = 0;
     HIPCHK(hipMemsetAsync(c->dstat, 0, 2 * sizeof(int), st));
-    if (ew & (2 | 8)) c->xgroup_ok = false;
+    if (ew & (2 | 8)) c->caps.xgroup_ok = false;
     return fail(DCTTS_ERR_STATE, "decode: an EARLIER decode on this context failed on the device (error word " + std::to_string(ew) + ") and dctts_decode_status was not consulted; its outputs were poisoned (NaN / -1)");
   }
   // Two host threads decoding on two contexts of one device must not both see the old lease and enqueue overlapping decodes: the device's lease is held from here to the
@@ -1357,12 +1325,9 @@ static int decode_impl(dctts_ctx* c, const int32_t* L, int B, int N, int T, floa
   c->fin_xerr = nullptr; c->fin_werr = nullptr;
   // dctts_decode_safe_once: THIS decode runs one launch per layer and meets the side stream through stream operations (no team kernel, no bounded in-kernel wait:
   // nothing in it can time out when the GPU is shared) -- the persistent settings (dctts_set_team_kernels, DCTTS_XGROUP / DCTTS_XCONE / DCTTS_CHAIN_WAIT,
-  // a switch-off by dctts_decode_status) are left exactly as they were
-  struct SafeOnce {
-    dctts_ctx* c; bool on; int xg, xc, cw;
-    explicit SafeOnce(dctts_ctx* c_) : c(c_), on(c_->safe_once && c_->safe_once_tid == std::this_thread::get_id()), xg(c_->xgroup), xc(c_->xcone), cw(c_->chain_wait_inkernel) { if (on) { c->safe_once = false; c->xgroup = 0; c->xcone = 0; c->chain_wait_inkernel = 0; } }
-    ~SafeOnce() { if (on) { c->xgroup = xg; c->xcone = xc; c->chain_wait_inkernel = cw; } }
-  } safe_once(c);
+  // a switch-off by dctts_decode_status) are left exactly as they were: the decode runs on a copy of them
+  DecodeKnobs knobs = c->knobs;
+  if (c->safe_once && c->safe_once_tid == std::this_thread::get_id()) { c->safe_once = false; knobs.xgroup = 0; knobs.xcone = 0; knobs.chain_wait_inkernel = 0; }
   DecodeWs w;
   CHK(decode_ws(c, B, N, T, &w, st));
   const bool v3 = (c->decode_mode == 3);
@@ -1385,7 +1350,7 @@ static int decode_impl(dctts_ctx* c, const int32_t* L, int B, int N, int T, floa
     HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));
     bool own = st && hipStreamGetPriority(st, &pr) == hipSuccess && pr == hi && hi != lo;
     if (!own) (void)hipGetLastError();
-    if (own && !c->sync_values) { c->own_tested = st; c->own_ok = true; }
+    if (own && !meets_through_counters(c)) { c->own_tested = st; c->own_ok = true; }
     if (own && st != c->own_tested) {        // ... and only if it does not share a hardware queue with the side stream (decode_streams_init; tested once per stream handle)
       bool ok = false;
       CHK(streams_run_concurrently(c, st, c->s_bulk, &ok));
@@ -1393,11 +1358,11 @@ static int decode_impl(dctts_ctx* c, const int32_t* L, int B, int N, int T, floa
     }
     if (own && !c->own_ok) own = false;
     if (own) {
-      CHK(decode_v3(c, w, B, N, T, st));
+      CHK(decode_v3(c, knobs, w, B, N, T, st));
     } else {
       HIPCHK(hipEventRecord(c->ev_in, st));
       HIPCHK(hipStreamWaitEvent(c->s_chain, c->ev_in, 0));
-      const int rc = decode_v3(c, w, B, N, T, c->s_chain);
+      const int rc = decode_v3(c, knobs, w, B, N, T, c->s_chain);
       HIPCHK(hipEventRecord(c->ev_out, c->s_chain));
       HIPCHK(hipStreamWaitEvent(st, c->ev_out, 0));
       CHK(rc);
@@ -1493,11 +1458,11 @@ extern "C" int dctts_decode_status(dctts_ctx* c) {
     (void)dev_zero_now(c->dstat, 2 * sizeof(int));
     // only a team that is not on one XCD (bits 2 / 8) says something permanent about this device; time-outs (bits 1 / 4 / 16 / 32: CUs or the side stream held
     // up by somebody else's work) are transient -- the team kernels stay on unless three reports in a row fail
-    if (ew & (2 | 8)) c->xgroup_ok = false;
-    else if (++c->team_fail_streak >= 3) c->xgroup_ok = false;
+    if (ew & (2 | 8)) c->caps.xgroup_ok = false;
+    else if (++c->team_fail_streak >= 3) c->caps.xgroup_ok = false;
     return fail(DCTTS_ERR_STATE, "decode: " + std::to_string(nfail) + " decode(s) failed on the device since the last report (error word " + std::to_string(ew) +
                 ": 1 / 2 = xgroup_kernel barrier time-out / a team not on one XCD, 4 / 8 = the same in xcone_kernel, 16 = the side stream never arrived, 32 = an in-kernel stream wait timed out, "
-                "64 = injected by the debug hook): their outputs were overwritten with NaN / -1" + (c->xgroup_ok ? "" : "; further decodes run one launch per layer"));
+                "64 = injected by the debug hook): their outputs were overwritten with NaN / -1" + (c->caps.xgroup_ok ? "" : "; further decodes run one launch per layer"));
   }
   c->team_fail_streak = 0;
   return 0;
@@ -1506,15 +1471,15 @@ extern "C" int dctts_decode_status(dctts_ctx* c) {
 extern "C" int dctts_set_team_kernels(dctts_ctx* c, int enable) {
   if (!c || enable < 0 || enable > 1) return fail(DCTTS_ERR_ARG, "team kernels: 0 or 1");
   std::lock_guard<std::recursive_mutex> lk_(c->mu);
-  c->xgroup = enable; c->xcone = enable;
-  if (enable) { c->xgroup_ok = true; c->team_fail_streak = 0; }
+  c->knobs.xgroup = enable; c->knobs.xcone = enable;
+  if (enable) { c->caps.xgroup_ok = true; c->team_fail_streak = 0; }
   return 0;
 }
 
 extern "C" int dctts_debug_team_kernels_state(dctts_ctx* c) {
   if (!c) return fail(DCTTS_ERR_ARG, "null ctx");
   std::lock_guard<std::recursive_mutex> lk_(c->mu);
-  return (c->xgroup ? 1 : 0) | (c->xcone ? 2 : 0) | (c->xgroup_ok ? 4 : 0);
+  return (c->knobs.xgroup ? 1 : 0) | (c->knobs.xcone ? 2 : 0) | (c->caps.xgroup_ok ? 4 : 0);
 }
 
 extern "C" int dctts_decode_safe_once(dctts_ctx* c) {

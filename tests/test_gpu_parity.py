@@ -355,7 +355,7 @@ def test_decode_vs_oracle_loop(weights, graph, mode):
     assert trajr.max() > 10
 
 
-@pytest.mark.parametrize("knob", ["DCTTS_SYNC_VALUES=0", "DCTTS_CHAIN_WAIT=0", "DCTTS_XGROUP=0", "DCTTS_XCONE=0", "DCTTS_XCONE=2", "DCTTS_XGROUP=0,DCTTS_XCONE=0", "DCTTS_CHAIN_TAIL=0", "DCTTS_CHAIN_TAIL=1", "DCTTS_CHAIN_TAIL=5", "DCTTS_CHAIN_TAIL=6", "DCTTS_CHAIN_TAIL=6,DCTTS_XCONE=2"])
+@pytest.mark.parametrize("knob", ["DCTTS_SYNC_VALUES=0", "DCTTS_CHAIN_WAIT=0", "DCTTS_XGROUP=0", "DCTTS_XCONE=0", "DCTTS_XCONE=2", "DCTTS_XGROUP=0,DCTTS_XCONE=0", "DCTTS_CHAIN_TAIL=0", "DCTTS_CHAIN_TAIL=1", "DCTTS_CHAIN_TAIL=5", "DCTTS_CHAIN_TAIL=6", "DCTTS_CHAIN_TAIL=6,DCTTS_XCONE=2", "DCTTS_CHAIN_TAIL=7"])
 def test_decode_stream_meeting_variants(weights, knob):
     """The chain and side streams of the decode meet inside kernels (default: counters polled / written by the launches themselves, passenger
     workgroups), with stream wait / write operations (DCTTS_CHAIN_WAIT=0), or through events (DCTTS_SYNC_VALUES=0: what rocprofv3 --pmc
@@ -364,8 +364,9 @@ def test_decode_stream_meeting_variants(weights, knob):
     2 (default) the whole chain piece as ONE launch (xchain_kernel, round 5: xtail_kernel's layers -- the newest-row layers HC_2 .. HC_4, HC_5 .. HC_7 over their
     few cone rows, the seven k = 1 layers -- a team barrier, then xgroup_kernel's AudioEnc run + attention + C_1), 6 the same as two launches (round 4's form),
     5 xtail_kernel behind an AudioDec run of xgroup_kernel (three launches), 1 xmlp_kernel (the k = 1 layers in team form, HC_5 .. HC_7 split between chain and
-    side stream), 0 mlp_rows_kernel (round 2's row-split form).  The knobs are read when a context is created.  Every
-    variant must reproduce the oracle loop: trajectory integer-exact."""
+    side stream), 0 mlp_rows_kernel (round 2's row-split form), 7 the default with round 5's split of the cone (three newest-row layers in front).  The knobs are
+    read when a context is created; dc_tts_amd/csrc/decode_form.h resolves them (tests/test_decode_form.py).  Every variant must reproduce the oracle loop:
+    trajectory integer-exact."""
     from dc_tts_amd.engine import Engine
     T = 100
     pairs = [kv.split("=") for kv in knob.split(",")]              # (both team kernels off = what a decode falls back to after a failed hand-off)
@@ -385,6 +386,33 @@ def test_decode_stream_meeting_variants(weights, knob):
         np.testing.assert_array_equal(mx.cpu().numpy(), trajr)
         assert maxabs(Y.cpu().numpy(), Yr) < TOL
     eng.close()
+
+
+def test_switching_forms_inside_one_context_serves_no_stale_table(weights):
+    """One engine, one geometry (B = 3, T = 100: the whole 85-row cone), four launch forms in a row: the default, the safe per-layer form for one decode
+    (dctts_decode_safe_once), the team kernels switched off, and on again.  The device tables and captured graphs are cached per geometry under the form's key
+    (decode_form.h: DecodeForm::key): every decode must reproduce the oracle, and the last one -- the default form again, served from the first one's tables --
+    must equal the first bit for bit."""
+    from dc_tts_amd.engine import Engine
+    T = 100
+    eng = Engine(weights, hp.replace(max_T=T))
+    L, Yr, trajr, gap = _oracle_decode(weights, T, 3, 21)
+    outs = []
+    try:
+        for step in ("default", "safe once", "team kernels off", "team kernels on"):
+            if step == "safe once": eng._ok(eng.lib.dctts_decode_safe_once(eng._h))
+            if step == "team kernels off": eng.set_team_kernels(False)
+            if step == "team kernels on": eng.set_team_kernels(True)
+            Y, mx = eng.text2mel(dev(L))
+            eng.synchronize()
+            np.testing.assert_array_equal(mx.cpu().numpy(), trajr, err_msg=step)
+            err = maxabs(Y.cpu().numpy(), Yr)
+            print(f"{step}: max|Y - oracle| = {err:.2e}")
+            assert err < TOL, step
+            outs.append((Y, mx))
+        assert torch.equal(outs[0][0], outs[-1][0]) and torch.equal(outs[0][1], outs[-1][1])
+    finally:
+        eng.close()
 
 
 @pytest.mark.parametrize("B", [8, 7, 12, 16])
