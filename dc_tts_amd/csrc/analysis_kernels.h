@@ -44,10 +44,11 @@ struct AnGeom {
 };
 
 // n_frames of an utterance whose (trimmed) signal is [s, e): -1 where reflect padding is undefined, 0 for nothing left
-__device__ __forceinline__ int an_frame_count(int len, int s, int e, int hop) {
-  if (len <= VOC_NFFT / 2) return -1;
+// (half = n_fft / 2 of the handle)
+__device__ __forceinline__ int an_frame_count(int len, int s, int e, int hop, int half) {
+  if (len <= half) return -1;
   if (e <= s) return 0;
-  return e - s <= VOC_NFFT / 2 ? -1 : 1 + (e - s) / hop;
+  return e - s <= half ? -1 : 1 + (e - s) / hop;
 }
 __device__ __forceinline__ void an_put_bounds(int b, int s, int e, int nf, int* __restrict__ ws, int* __restrict__ bounds,
                                               int* __restrict__ n_frames) {
@@ -58,12 +59,12 @@ __device__ __forceinline__ void an_put_bounds(int b, int s, int e, int nf, int* 
 __device__ __forceinline__ int an_len(const int* __restrict__ lengths, int b, int Lmax) { return min(max(lengths[b], 0), Lmax); }
 
 // trim = 0.  grid (ceil(B / 64)), block 64.
-AN_KERNEL void __launch_bounds__(64) full_bounds_kernel(const int* __restrict__ lengths, int B, int Lmax, int hop, int* __restrict__ ws,
+AN_KERNEL void __launch_bounds__(64) full_bounds_kernel(const int* __restrict__ lengths, int B, int Lmax, int hop, int half, int* __restrict__ ws,
                                                          int* __restrict__ bounds, int* __restrict__ n_frames) {
   const int b = blockIdx.x * 64 + threadIdx.x;
   if (b >= B) return;
   const int len = an_len(lengths, b, Lmax);
-  an_put_bounds(b, 0, len, an_frame_count(len, 0, len, hop), ws, bounds, n_frames);
+  an_put_bounds(b, 0, len, an_frame_count(len, 0, len, hop, half), ws, bounds, n_frames);
 }
 
 // frame_power_kernel for a ragged batch: utterance b has lengths[b] samples of its Lmax-long row; frames past its own count, and an
@@ -91,13 +92,13 @@ AN_KERNEL void __launch_bounds__(256) frame_power_ragged_kernel(const float* __r
 // trim_bounds_kernel for a ragged batch, plus the frame count the analysis kernel needs.  A clip whose loudest frame has no power at all
 // keeps nothing (n_frames 0).  grid (B), block 256.
 AN_KERNEL void __launch_bounds__(256) trim_bounds_ragged_kernel(const float* __restrict__ pw, const int* __restrict__ lengths,
-                                                                 int Lmax, int n_tf, int flen, int fhop, float top_db, int hop,
+                                                                 int Lmax, int n_tf, int flen, int fhop, float top_db, int hop, int half,
                                                                  int* __restrict__ ws, int* __restrict__ bounds, int* __restrict__ n_frames) {
   __shared__ float smax[256];
   __shared__ int sfirst[256], slast[256];
   const int tid = threadIdx.x, b = blockIdx.x;
   const int L = an_len(lengths, b, Lmax);
-  if (L <= flen / 2 || L <= VOC_NFFT / 2) {                  // uniform
+  if (L <= flen / 2 || L <= half) {                  // uniform
     if (tid == 0) an_put_bounds(b, 0, L, -1, ws, bounds, n_frames);
     return;
   }
@@ -124,7 +125,7 @@ AN_KERNEL void __launch_bounds__(256) trim_bounds_ragged_kernel(const float* __r
   if (tid == 0) {
     int s = 0, e = 0;
     if (slast[0] >= 0) { s = sfirst[0] * fhop; e = (slast[0] + 1) * fhop; if (e > L) e = L; }
-    an_put_bounds(b, s, e, an_frame_count(L, s, e, hop), ws, bounds, n_frames);
+    an_put_bounds(b, s, e, an_frame_count(L, s, e, hop, half), ws, bounds, n_frames);
   }
 }
 

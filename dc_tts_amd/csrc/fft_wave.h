@@ -113,4 +113,15 @@ template <bool INV> FW_HD void fw_passC_load(float2 v[16], const float2* ex, int
   }
 }
 
+// ---- two real sequences a, b through ONE transform (pair_kernels.h): z = a + i b, Z = FFT(z), and with c = Z[N - k] (Z[N] = Z[0])
+//   A[k] = (Z[k] + conj c) / 2,   B[k] = (Z[k] - conj c) / (2 i)
+// are the full Hermitian spectra of a and b.  The lane that owns N - k calls this with the arguments swapped and gets conj A[k], conj B[k]
+// BITWISE (x + y = y + x, x - y = -(y - x) in IEEE arithmetic): no lane ever has to be told its partner's result.
+FW_HD void fw_pair_split(float2 z, float2 c, float2& A, float2& B) {
+  A = fw_f2(0.5f * (z.x + c.x), 0.5f * (z.y - c.y));
+  B = fw_f2(0.5f * (z.y + c.y), 0.5f * (c.x - z.x));
+}
+// Z'[k] = XA[k] + i XB[k]: the inverse transform of Z' is a' + i b' when XA, XB are Hermitian
+FW_HD float2 fw_pair_merge(float2 XA, float2 XB) { return fw_f2(XA.x - XB.y, XA.y + XB.x); }
+
 }  // namespace dctts

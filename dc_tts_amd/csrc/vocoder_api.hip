@@ -16,6 +16,7 @@
 #include "api_common.h"
 #include "vocoder_kernels.h"
 #include "analysis_kernels.h"
+#include "pair_kernels.h"
 
 using namespace dctts;
 
@@ -33,6 +34,7 @@ struct dctts_vocoder {
   dctts_vocoder_config cfg;
   int device = 0;
   int lpad = 0, frs = 0;
+  int nfft = VOC_NFFT, bins = VOC_BINS;      // 2048 / 1025: vocoder_kernels.h, analysis_kernels.h;  1024 / 513: pair_kernels.h (two frames per transform)
   float *window = nullptr, *wss = nullptr;
   float2 *w1024 = nullptr, *w2048 = nullptr;
   int wss_frames = 0;
@@ -79,7 +81,8 @@ static int vgrow(VBuf& b, size_t bytes) {
 
 extern "C" int dctts_vocoder_create(dctts_vocoder** out, int device, const dctts_vocoder_config* cfg) {
   if (!out || !cfg) return dctts_set_error(DCTTS_ERR_ARG, "null argument");
-  if (cfg->n_fft != VOC_NFFT) return dctts_set_error(DCTTS_ERR_ARG, "the FFT kernels are specialised for n_fft == 2048");
+  if (cfg->n_fft != VOC_NFFT && cfg->n_fft != PAIR_N)
+    return dctts_set_error(DCTTS_ERR_ARG, "the FFT kernels are built for n_fft == 2048 (one frame per transform) and n_fft == 1024 (two frames per transform)");
   if (cfg->win_length < 2 || cfg->win_length > cfg->n_fft || cfg->hop_length < 1 || cfg->hop_length > cfg->win_length)
     return dctts_set_error(DCTTS_ERR_ARG, "need 1 <= hop_length <= win_length <= n_fft");
   if (cfg->n_iter < 0 || cfg->trim_frame_length < 2 || cfg->trim_hop_length < 1)
@@ -87,11 +90,12 @@ extern "C" int dctts_vocoder_create(dctts_vocoder** out, int device, const dctts
   VHIPCHK(hipSetDevice(device));
   dctts_vocoder* v = new dctts_vocoder();
   v->cfg = *cfg; v->device = device;
+  v->nfft = cfg->n_fft; v->bins = 1 + cfg->n_fft / 2;
   if (const char* e = getenv("DCTTS_VOC_WAVE")) v->wave_kernel = atoi(e);
   v->lpad = (cfg->n_fft - cfg->win_length) / 2;                      // librosa.util.pad_center
   v->frs = (cfg->win_length + 3) & ~3;
   // periodic Hann (scipy get_window('hann', win, fftbins=True)), evaluated in double, rounded once
-  std::vector<float> w(VOC_NFFT, 0.f);
+  std::vector<float> w(v->nfft, 0.f);
   for (int n = 0; n < cfg->win_length; ++n)
     w[v->lpad + n] = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)n / (double)cfg->win_length));
   std::vector<float2> t1(VOC_M), t2(VOC_M + 1);
@@ -99,10 +103,10 @@ extern "C" int dctts_vocoder_create(dctts_vocoder** out, int device, const dctts
   for (int k = 0; k <= VOC_M; ++k) t2[k] = make_float2((float)std::cos(2.0 * M_PI * k / VOC_NFFT), (float)-std::sin(2.0 * M_PI * k / VOC_NFFT));
   VHIPCHK(hipMalloc((void**)&v->window, w.size() * sizeof(float)));
   VHIPCHK(hipMalloc((void**)&v->w1024, t1.size() * sizeof(float2)));
-  VHIPCHK(hipMalloc((void**)&v->w2048, t2.size() * sizeof(float2)));
+  if (v->nfft == VOC_NFFT) VHIPCHK(hipMalloc((void**)&v->w2048, t2.size() * sizeof(float2)));      // (the pair form has no twist)
   VHIPCHK(hipMemcpy(v->window, w.data(), w.size() * sizeof(float), hipMemcpyHostToDevice));
   VHIPCHK(hipMemcpy(v->w1024, t1.data(), t1.size() * sizeof(float2), hipMemcpyHostToDevice));
-  VHIPCHK(hipMemcpy(v->w2048, t2.data(), t2.size() * sizeof(float2), hipMemcpyHostToDevice));
+  if (v->w2048) VHIPCHK(hipMemcpy(v->w2048, t2.data(), t2.size() * sizeof(float2), hipMemcpyHostToDevice));
   *out = v;
   return 0;
 }
@@ -128,12 +132,12 @@ extern "C" int dctts_vocoder_destroy(dctts_vocoder* v) {
 static int ensure_wss(dctts_vocoder* v, int F) {
   if (v->wss_frames == F) return 0;
   const int hop = v->cfg.hop_length, win = v->cfg.win_length;
-  std::vector<float> w2(VOC_NFFT, 0.f);
+  std::vector<float> w2(v->nfft, 0.f);
   for (int n = 0; n < win; ++n) {
     const float w = (float)(0.5 - 0.5 * std::cos(2.0 * M_PI * (double)n / (double)win));
     w2[v->lpad + n] = w * w;
   }
-  std::vector<float> acc((size_t)VOC_NFFT + (size_t)hop * (F - 1), 0.f);
+  std::vector<float> acc((size_t)v->nfft + (size_t)hop * (F - 1), 0.f);
   for (int i = 0; i < F; ++i) {
     float* a = acc.data() + (size_t)i * hop;
     for (int n = v->lpad; n < v->lpad + win; ++n) a[n] = a[n] + w2[n];
@@ -149,17 +153,18 @@ static int ensure_wss(dctts_vocoder* v, int F) {
 static int geom(dctts_vocoder* v, int B, int F, VocGeom* g) {
   if (B < 1 || F < 1) return dctts_set_error(DCTTS_ERR_ARG, "B and F must be positive");
   const long L = (long)v->cfg.hop_length * (F - 1);
-  if (L <= VOC_NFFT / 2) return dctts_set_error(DCTTS_ERR_ARG, "too few frames: reflect padding needs hop*(F-1) > n_fft/2 (librosa raises too)");
+  if (L <= v->nfft / 2) return dctts_set_error(DCTTS_ERR_ARG, "too few frames: reflect padding needs hop*(F-1) > n_fft/2 (librosa raises too)");
   if (L > 0x3fffffff) return dctts_set_error(DCTTS_ERR_ARG, "utterance too long");
   VCHK(ensure_wss(v, F));
   g->F = F; g->L = (int)L; g->hop = v->cfg.hop_length; g->win = v->cfg.win_length; g->lpad = v->lpad; g->frs = v->frs;
   g->window = v->window; g->wss = v->wss; g->w1024 = v->w1024; g->w1024i = v->w1024; g->w2048 = v->w2048;
   g->tiny = std::numeric_limits<float>::min();
   g->dmax = (v->cfg.win_length + v->cfg.hop_length - 1) / v->cfg.hop_length;
+  g->nfft = v->nfft;
   return 0;
 }
 
-// utils.py:96-106 on device buffers.  spec (B,F,1025) magnitudes -> y (B, L).
+// utils.py:96-106 on device buffers.  spec (B,F,1+n_fft/2) magnitudes -> y (B, L).
 // With momentum (vocoder_kernels.h, gl_iter_wave_body<MOM>) iteration `it` analyses y_it - beta * y_{it-1}, so two signal buffers alternate: pass j
 // (0 = the zero-phase istft, it + 1 = the overlap-add of iteration it) writes the caller's y when n_iter - j is even and ymom otherwise.  The last pass
 // lands in y, the overlap-add of iteration it overwrites y_{it-1} after the iteration kernel has read it (stream order), and both buffers are written
@@ -172,23 +177,34 @@ static int run_griffin_lim(dctts_vocoder* v, const VocGeom& g, const float* spec
   if (mom) VCHK(vgrow(v->ymom, (size_t)B * g.L * sizeof(float)));
   const float beta = (float)((double)v->momentum / (1.0 + (double)v->momentum));
   auto ybuf = [&](int j) -> float* { return mom && ((n_iter - j) & 1) ? (float*)v->ymom.p : y; };
-  const dim3 grid(g.F, B), ogrid((g.L + 255) / 256, B);
-  const int n_items = B * g.F, per_xcd = (n_items + 7) / 8;
-  hipLaunchKernelGGL(istft_frames_kernel, grid, dim3(VOC_THREADS), 0, st, g, (const float2*)nullptr, spec, fr);
+  const bool pair = v->nfft == PAIR_N;     // two frames per transform (pair_kernels.h): half the workgroups in every frame-wise launch
+  const int fitems = pair ? (g.F + 1) / 2 : g.F;
+  const dim3 grid(fitems, B), ogrid((g.L + 255) / 256, B);
+  const int n_items = B * fitems, per_xcd = (n_items + 7) / 8;
+  auto istft_frames = [&](const float2* X, float* out) {
+    if (pair) hipLaunchKernelGGL(istft_frames_pair_kernel, grid, dim3(VOC_THREADS), 0, st, g, X, spec, out);
+    else hipLaunchKernelGGL(istft_frames_kernel, grid, dim3(VOC_THREADS), 0, st, g, X, spec, out);
+  };
+  istft_frames(nullptr, fr);
   hipLaunchKernelGGL(ola_kernel, ogrid, dim3(256), 0, st, g, (const float*)fr, ybuf(0));
   for (int it = 0; it < n_iter; ++it) {
     const float* ycur = ybuf(it);
     float* ynext = ybuf(it + 1);           // with momentum also y_{it-1}, which this iteration reads before its overlap-add replaces it
     if (X_best && it == n_iter - 1) {      // the caller wants the last X_best: un-fused pair for this iteration
-      hipLaunchKernelGGL(stft_phase_kernel, grid, dim3(VOC_THREADS), 0, st, g, (const float*)fr, spec, X_best);
+      if (pair) hipLaunchKernelGGL(stft_phase_pair_kernel, grid, dim3(VOC_THREADS), 0, st, g, (const float*)fr, spec, X_best);
+      else hipLaunchKernelGGL(stft_phase_kernel, grid, dim3(VOC_THREADS), 0, st, g, (const float*)fr, spec, X_best);
       VCHK(vgrow(v->fr1, (size_t)B * g.F * g.frs * sizeof(float)));
-      hipLaunchKernelGGL(istft_frames_kernel, grid, dim3(VOC_THREADS), 0, st, g, (const float2*)X_best, spec, (float*)v->fr1.p);
+      istft_frames((const float2*)X_best, (float*)v->fr1.p);
       hipLaunchKernelGGL(ola_kernel, ogrid, dim3(256), 0, st, g, (const float*)v->fr1.p, y);
       break;
     }
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (v->prof) { VHIPCHK(hipEventCreate(&e0)); VHIPCHK(hipEventCreate(&e1)); VHIPCHK(hipEventRecord(e0, st)); }
-    if (mom && it > 0)                     // (one register budget only: the 4-waves build of this form measured slower and spills)
+    if (pair && mom && it > 0)
+      hipLaunchKernelGGL(gl_iter_pair_mom_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, ycur, (const float*)ynext, beta, spec, fr, n_items, per_xcd);
+    else if (pair)
+      hipLaunchKernelGGL(gl_iter_pair_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, ycur, spec, fr, n_items, per_xcd);
+    else if (mom && it > 0)                // (one register budget only: the 4-waves build of this form measured slower and spills)
       hipLaunchKernelGGL(gl_iter_wave_mom_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, ycur, (const float*)ynext, beta, spec, fr, n_items, per_xcd);
     else if (v->wave_kernel == 2)
       hipLaunchKernelGGL(gl_iter_wave4_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, ycur, spec, fr, n_items, per_xcd);
@@ -228,7 +244,7 @@ extern "C" int dctts_spectrogram2wav(dctts_vocoder* v, const float* mag, int B, 
   VocGeom g;
   VCHK(geom(v, B, F, &g));
   if (bounds && g.L <= v->cfg.trim_frame_length / 2) return dctts_set_error(DCTTS_ERR_ARG, "utterance shorter than the trim frame's reflect padding");      // (before anything is launched)
-  const long n = (long)B * F * VOC_BINS;
+  const long n = (long)B * F * v->bins;
   VCHK(vgrow(v->spec, (size_t)n * sizeof(float)));
   VCHK(vgrow(v->yraw, (size_t)B * g.L * sizeof(float)));
   float* spec = (float*)v->spec.p; float* yraw = (float*)v->yraw.p;
@@ -262,9 +278,9 @@ extern "C" int dctts_vocoder_set_mel_basis(dctts_vocoder* v, const float* basis_
   std::vector<int4> bands((size_t)n_mels);
   std::vector<float> w;
   for (int m = 0; m < n_mels; ++m) {
-    const float* row = basis_host + (size_t)m * VOC_BINS;
-    int lo = VOC_BINS, hi = -1;
-    for (int k = 0; k < VOC_BINS; ++k) if (row[k] != 0.f) { if (k < lo) lo = k; hi = k; }
+    const float* row = basis_host + (size_t)m * v->bins;
+    int lo = v->bins, hi = -1;
+    for (int k = 0; k < v->bins; ++k) if (row[k] != 0.f) { if (k < lo) lo = k; hi = k; }
     const int width = hi < 0 ? 0 : hi - lo + 1;
     if (hi < 0) lo = 0;
     for (int k = lo; k < lo + width; ++k)
@@ -294,7 +310,7 @@ extern "C" int dctts_wav2spectrograms(dctts_vocoder* v, const float* wav, const 
                                       float* mel, float* mag, int32_t* n_frames, int32_t* bounds, void* stream) {
   if (!v || !wav || !lengths) return dctts_set_error(DCTTS_ERR_ARG, "null argument");
   if (B < 1 || r < 1) return dctts_set_error(DCTTS_ERR_ARG, "B and r must be positive");
-  if (Lmax <= VOC_NFFT / 2) return dctts_set_error(DCTTS_ERR_ARG, "Lmax must exceed n_fft/2 (reflect padding)");
+  if (Lmax <= v->nfft / 2) return dctts_set_error(DCTTS_ERR_ARG, "Lmax must exceed n_fft/2 (reflect padding)");
   if (Lmax > 0x3fffffff) return dctts_set_error(DCTTS_ERR_ARG, "utterance too long");
   const int hop = v->cfg.hop_length;
   const int Fmax = 1 + Lmax / hop, Fpad = (Fmax + r - 1) / r * r;
@@ -313,9 +329,9 @@ extern "C" int dctts_wav2spectrograms(dctts_vocoder* v, const float* wav, const 
     VCHK(vgrow(v->pw, (size_t)B * n_tf * sizeof(float)));
     hipLaunchKernelGGL(frame_power_ragged_kernel, dim3(n_tf, B), dim3(256), 0, st, wav, (const int*)lengths, (float*)v->pw.p, Lmax, n_tf, flen, fhop);
     hipLaunchKernelGGL(trim_bounds_ragged_kernel, dim3(B), dim3(256), 0, st, (const float*)v->pw.p, (const int*)lengths, Lmax, n_tf, flen, fhop,
-                       v->cfg.trim_top_db, hop, ws, (int*)bounds, (int*)n_frames);
+                       v->cfg.trim_top_db, hop, v->nfft / 2, ws, (int*)bounds, (int*)n_frames);
   } else {
-    hipLaunchKernelGGL(full_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, st, (const int*)lengths, B, Lmax, hop, ws, (int*)bounds, (int*)n_frames);
+    hipLaunchKernelGGL(full_bounds_kernel, dim3((B + 63) / 64), dim3(64), 0, st, (const int*)lengths, B, Lmax, hop, v->nfft / 2, ws, (int*)bounds, (int*)n_frames);
   }
   if (mel || mag) {
     AnGeom g;
@@ -323,8 +339,10 @@ extern "C" int dctts_wav2spectrograms(dctts_vocoder* v, const float* wav, const 
     g.hop = hop;
     g.preemph = v->cfg.preemphasis; g.max_db = v->cfg.max_db; g.ref_db = v->cfg.ref_db;
     g.window = v->window; g.w1024 = v->w1024; g.w2048 = v->w2048; g.bands = v->bands; g.bandw = v->bandw;
-    const int n_items = B * Fpad, per_xcd = (n_items + 7) / 8;
-    if ((v->lpad >> 7) >= 3 && ((v->lpad + v->cfg.win_length - 1) >> 7) <= 12)      // the window's first and last lane-strided slot
+    const int n_items = v->nfft == PAIR_N ? B * ((Fpad + 1) / 2) : B * Fpad, per_xcd = (n_items + 7) / 8;
+    if (v->nfft == PAIR_N)                  // one wave per frame pair of an utterance
+      hipLaunchKernelGGL(analysis_pair_kernel, dim3(8 * per_xcd), dim3(64), 0, st, g, wav, (const int*)ws, mag, mel, n_items, per_xcd);
+    else if ((v->lpad >> 7) >= 3 && ((v->lpad + v->cfg.win_length - 1) >> 7) <= 12)      // the window's first and last lane-strided slot
       hipLaunchKernelGGL((analysis_wave_kernel<3, 12>), dim3(8 * per_xcd), dim3(64), 0, st, g, wav, (const int*)ws, mag, mel, n_items, per_xcd);
     else
       hipLaunchKernelGGL((analysis_wave_kernel<0, 15>), dim3(8 * per_xcd), dim3(64), 0, st, g, wav, (const int*)ws, mag, mel, n_items, per_xcd);

@@ -39,6 +39,7 @@ struct VocGeom {
   const float2* w2048;     // exp(-2 pi i k / 2048), k <= 1024
   float tiny;
   int dmax;         // ceil(win / hop): frames f-dmax .. f+dmax can overlap frame f's window
+  int nfft;         // 2048 (the kernels of this file) or 1024 (pair_kernels.h); the overlap-add below serves both
 };
 
 __device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
@@ -277,14 +278,14 @@ gl_iter_wave_mom_kernel(const VocGeom g, const float* __restrict__ y, const floa
 // 256 consecutive samples are a block-uniform range (scalar divisions, <= dmax + 2 of them); each lane just tests its index.
 __global__ void __launch_bounds__(256) ola_kernel(const VocGeom g, const float* __restrict__ fr, float* __restrict__ y) {
   const int b = blockIdx.y;
-  const int m0 = blockIdx.x * 256 + VOC_NFFT / 2;           // first y_full index of the block (uniform)
+  const int m0 = blockIdx.x * 256 + g.nfft / 2;             // first y_full index of the block (uniform)
   const int lo_num = m0 - (g.lpad + g.win - 1);
   int q_lo = lo_num <= 0 ? 0 : (lo_num + g.hop - 1) / g.hop;
   int q_hi = (m0 + 255 - g.lpad) / g.hop;
   if (q_hi > g.F - 1) q_hi = g.F - 1;
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= g.L) return;
-  const int m = n + VOC_NFFT / 2;
+  const int m = n + g.nfft / 2;
   const float* fr_b = fr + (long)b * g.F * g.frs;
   float acc = 0.f;
   for (int q = q_lo; q <= q_hi; ++q) {                       // ascending frame order, as librosa.istft accumulates

@@ -186,7 +186,8 @@ typedef struct dctts_vocoder dctts_vocoder;
 
 /* hyperparams.py:13-24 + the librosa.effects.trim defaults the reference relies on (utils.py:92) */
 typedef struct {
-  int n_fft;            /* 2048 (the FFT kernels are specialised on it) */
+  int n_fft;            /* 2048 (the reference: one frame per 1024-point complex transform, 1025 bins) or 1024 (two adjacent frames per transform,
+                         * 513 bins); anything else is DCTTS_ERR_ARG */
   int hop_length;       /* 275 */
   int win_length;       /* 1102 */
   int n_iter;           /* 50 */
@@ -237,7 +238,10 @@ int dctts_vocoder_set_momentum(dctts_vocoder* v, float momentum);
  *   padding; 0 = nothing left (a clip of zeros; the numpy path keeps such a clip whole and returns floor values); -1 = the untrimmed or the trimmed signal
  *   has at most n_fft/2 samples, where reflect padding is undefined (all its rows are 0.0).  Neither touches the other utterances.
  * Stream-ordered, no host synchronisation (workspaces grow with the largest call); results are bitwise reproducible and do not depend on the rest of the
- * batch.  Lmax must exceed n_fft/2.  The trim decision is taken in fp32, the transform too (audio.py: float64). */
+ * batch.  Lmax must exceed n_fft/2.  The trim decision is taken in fp32, the transform too (audio.py: float64).
+ * Cross-talk at n_fft = 1024: frames 2p and 2p + 1 of an utterance share one fp32 transform, so a frame's rounding error is relative to the LOUDER of the
+ * two, not to itself (about 1e-7 of the louder frame's peak).  At ordinary levels that is below the normalisation floor of 1e-5; a frame 60 dB or more
+ * under its neighbour (the first frame of an onset) carries it visibly in its weakest bins.  n_fft = 2048 has one frame per transform and no such term. */
 int dctts_vocoder_set_mel_basis(dctts_vocoder* v, const float* basis_host, int n_mels);
 int dctts_wav2spectrograms(dctts_vocoder* v, const float* wav, const int32_t* lengths, int B, int Lmax, int trim, int r,
                            float* mel, float* mag, int32_t* n_frames, int32_t* bounds, void* stream);
